@@ -2,13 +2,18 @@
 """bench.py -- the BASELINE.json metric (Mpixels/s on the 16k x 16k Lanczos3 reduce) and the
 other BASELINE configurations as parity-checked measurements.
 
-  python bench.py --gpus 1 --steps K --warmup W [--config c2|c3|c4|c5slab|c5]
+  python bench.py --gpus 1 --steps K --warmup W [--config c2|c3|c4|c5slab|c5] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ... [--config c2|c4|c5]
 
 --config c2 (default): one "step" = one pass of vips_reduce(8, 8, kernel=lanczos3) (BASELINE
 configs[1]: 16384x16384 uchar RGBA -> 2048x2048) over one synthetic image that is already
 resident in HBM when the timed region starts; pixels counted are INPUT pixels of the first op
-(SURVEY.md 8(d)).  The JSON line also carries
+(SURVEY.md 8(d)).
+
+A plain run does only what the headline figure needs: set up, W warm-up steps, exactly K timed
+steps, the outputs (--dump-outputs), the result line (`value`, `ms_per_step`; `roofline`, `parity`
+and `cpu_baseline` are null).  --full adds everything else, and with it (c2) the JSON line also
+carries
 
   roofline      dominant kernel: algorithmic bytes per launch / mean launch duration, measured
                 with HIP events on the stream the kernel runs on (the library's gates)
@@ -31,6 +36,13 @@ resident in HBM when the timed region starts; pixels counted are INPUT pixels of
           exchange over RCCL (libvips_amd.sharding.exchange_halos) -> conv on the strip; strong
           scaling; every rank checks rows of its strip against the reference
 
+Without --full the other configurations skip their reference comparisons and CPU baselines too.
+
+--dump-outputs DIR (c2): after the timed steps, what the last timed step computed -- the reduced
+image a caller receives -- as DIR/reduce.npy in float32 (the uchar values, exact).  Where that
+would pass DUMP_LIMIT_BYTES, a fixed, seeded sample of its rows is kept, in order.  The input is
+the same seeded image on every run, so two builds can be compared output for output.
+
 N > 1 timing: barrier + synchronize on both sides, MAX over ranks, value = all ranks' pixels / that.
 """
 import argparse
@@ -48,6 +60,27 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec
 FP64_PEAK_TFLOPS = 78.6  # MI355X FP64 vector / matrix peak
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # --dump-outputs: all files together (the whole C2 output in float32 is 64 MiB)
+DUMP_SEED = 12345
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of {name: array} as <path>/<name>.npy in float32.  If they would pass
+    DUMP_LIMIT_BYTES together, the small ones are written whole and each of the others keeps a fixed, seeded
+    sample of its rows (axis 0, in order) in its share of what is left: the same rows on every run with the same
+    arguments."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: np.asarray(a, dtype=np.float32) for name, a in arrays.items()}
+    left = DUMP_LIMIT_BYTES
+    for i, name in enumerate(sorted(arrays, key=lambda k: arrays[k].nbytes)):
+        a = arrays[name]
+        share = left // (len(arrays) - i)
+        if a.nbytes > share and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, min(a.shape[0], share // max(1, a.nbytes // a.shape[0])))
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes
 
 
 def fp64_stream_tflops():
@@ -398,8 +431,10 @@ def run_c2(ctx, args):
     # never instead of it.
     elapsed, out = ctx.timed(step, args.steps, args.warmup)
     region_ms = ctx.event_ms / args.steps  # one launch per step: the kernel's average launch duration
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, {"reduce": out.numpy()})
     settled = None
-    if not args.no_settle:
+    if args.full and not args.no_settle:
         info = ctx.settle(step)
         elapsed2, out = ctx.timed(step, args.steps, args.warmup)
         settled = {"ms_per_step": round(elapsed2 / args.steps * 1e3, 4),
@@ -413,7 +448,7 @@ def run_c2(ctx, args):
 
     # ---- roofline of the dominant kernel: HIP events around every launch, on its stream
     roofline = None
-    report = ctx.gates(step, max(3, min(args.steps, 20)))
+    report = ctx.gates(step, max(3, min(args.steps, 20))) if args.full else None
     oh = ow = int(n / shrink + 0.5)
     # algorithmic bytes per launch (read each input byte once, write each
     # output byte once), per kernel of the pipeline
@@ -476,9 +511,10 @@ def run_c2(ctx, args):
     # host cores (rank 0, N = 1 only)
     parity = None
     cpu_baseline = None
-    helpers = ref_or_none()
-    if ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
+    if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_cpu_baseline:
         from tests import helpers as th
+
+        helpers = ref_or_none()
 
         host = src.cpu().numpy()
         got = out.numpy()
@@ -1469,16 +1505,26 @@ def main():
                     help="c2: time the first W + K launches of the process only (no clock-settling phase)")
     ap.add_argument("--no-configs", action="store_true", help="c2: leave the C3/C4/C5 entries out")
     ap.add_argument("--no-verify", action="store_true", help="skip the comparisons with the reference")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: clock settling, roofline and per-kernel gate times, "
+                         "the comparisons with the reference, CPU baselines, (c2) the other configurations and the "
+                         "single-call table, the full table as a file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="c2: write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.config != "c2":
+        ap.error("--dump-outputs is implemented for --config c2")
 
     ctx = Ctx(args)
-    verify = not args.no_verify
-    cpu = not args.no_cpu_baseline and ctx.rank == 0 and ctx.world == 1
+    verify = args.full and not args.no_verify
+    cpu = args.full and not args.no_cpu_baseline and ctx.rank == 0 and ctx.world == 1
     line = None
     if args.config == "c2":
         args.size = args.size or 16384
         line = run_c2(ctx, args)
-        if ctx.rank == 0 and ctx.world == 1 and not args.no_configs and args.size == 16384:
+        if args.full and ctx.rank == 0 and ctx.world == 1 and not args.no_configs and args.size == 16384:
             k = max(2, min(args.steps, 5))
             line["configs"] = [
                 run_c1(ctx, 20, 3, verify, cpu),
@@ -1525,11 +1571,13 @@ def main():
         size = args.size or 65536
         line = run_c5(ctx, args.steps, args.warmup, verify, width=size, im_height=size)
     if ctx.rank == 0:
-        # the full table first (a file, and an earlier stdout line with a prefix no JSON reader takes for a
-        # record), then the compact record as the LAST line: that is the one the driver parses
-        full_path = write_full(line)
-        print("bench_full " + json.dumps(line))
-        sys.stdout.flush()
+        # --full: the full table first (a file, and an earlier stdout line with a prefix no JSON reader takes
+        # for a record), then the compact record as the LAST line: that is the one the driver parses
+        full_path = None
+        if args.full:
+            full_path = write_full(line)
+            print("bench_full " + json.dumps(line))
+            sys.stdout.flush()
         print(json.dumps(final_line(line, full_path), allow_nan=False))
     ctx.close()
 

@@ -118,10 +118,13 @@ g++ -shared "$OUT"/obj/*.o -o "$OUT/lib/libvips.so" \
 	-L"$GLIB_PREFIX/lib" -Wl,-rpath,"$GLIB_PREFIX/lib" \
 	-lgio-2.0 -lgobject-2.0 -lgmodule-2.0 -lglib-2.0 -lexpat $JPEG_LIB -lm -lpthread
 
-# 7. the reference's own CLI tools, unchanged, for config C1
+# 7. the reference's own CLI tools, unchanged, for config C1.  They find libvips.so relative to
+# themselves ($ORIGIN), so that oracle/_ref/ still works after the tree has moved to another path,
+# else where it was built (the loader expands $ORIGIN of a program from /proc/self/exe; the tests
+# also put oracle/_ref/lib on LD_LIBRARY_PATH: tests/helpers.ref_cli_env).
 for t in vips vipsthumbnail vipsheader; do
 	gcc -std=gnu99 $CFLAGS_COMMON "$REF/tools/$t.c" -o "$OUT/bin/$t" \
-		-L"$OUT/lib" -lvips -Wl,-rpath,"$OUT/lib" \
+		-L"$OUT/lib" -lvips -Wl,-rpath,'$ORIGIN/../lib' -Wl,-rpath,"$OUT/lib" \
 		-L"$GLIB_PREFIX/lib" -Wl,-rpath,"$GLIB_PREFIX/lib" \
 		-lgio-2.0 -lgobject-2.0 -lgmodule-2.0 -lglib-2.0 -lm
 done

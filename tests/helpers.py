@@ -15,6 +15,16 @@ REF_LIB = os.path.join(ROOT, "oracle", "_ref", "lib", "libref_shim.so")
 PORT_LIB = os.path.join(ROOT, "oracle", "_build", "liboracle_port.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 MODULE_LIB = os.path.join(ROOT, "host", "_build", "vips-hip.so")
+REF_LIBDIR = os.path.join(ROOT, "oracle", "_ref", "lib")
+
+
+def ref_cli_env(**extra):
+    """The environment to run the reference's own CLI tools (oracle/_ref/bin) in: their libvips.so is put on
+    LD_LIBRARY_PATH, so that they load wherever the tree lies -- also where the loader cannot expand $ORIGIN for a
+    program (it reads /proc/self/exe for that)."""
+    env = dict(os.environ, **extra)
+    env["LD_LIBRARY_PATH"] = os.pathsep.join(p for p in (REF_LIBDIR, env.get("LD_LIBRARY_PATH")) if p)
+    return env
 
 FORMAT_DTYPES = {
     0: np.uint8, 1: np.int8, 2: np.uint16, 3: np.int16, 4: np.uint32,

@@ -1,10 +1,12 @@
 """CPU: the parts of bench.py that decide what evidence the driver's record holds -- the HBM-traffic stamp
 (profiles/traffic.json is only reported while its `isa_sha` equals the hash of the C2 kernel's machine code in the
 built library), the single-call table's entries VERDICT r4 asked for, and the scalars compact_summary() puts into
-`roofline` and the trailing `summary` object.  No device, no oracle: pure host code."""
+`roofline` and the trailing `summary` object, what --dump-outputs writes.  No device, no oracle: pure host code --
+except the one GPU test of a plain run."""
 import json
 import os
 
+import numpy as np
 import pytest
 
 import bench
@@ -151,3 +153,49 @@ def test_main_prints_the_compact_record_last(monkeypatch, capsys, tmp_path):
     assert full_path == os.path.join("gpurun_out", "bench_full.json")
     stored = json.load(open(os.path.join(str(tmp_path), full_path)))
     assert len(stored["ops"]) == 26 and stored["configs"][0]["name"] == "c3"
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """--dump-outputs: float32 .npy files; an output past the limit keeps a fixed, seeded sample of its rows, in order
+    (the C2 output, 2048 x 2048 x 4, is 64 MiB in float32)."""
+    small = np.arange(24, dtype=np.uint8).reshape(2, 3, 4)
+    big = np.broadcast_to(np.arange(2048, dtype=np.uint16)[:, None, None], (2048, 2048, 4))  # row r holds r
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "reduce": big})
+    sizes = [os.path.getsize(str(tmp_path / "a" / f)) for f in ("small.npy", "reduce.npy")]
+    assert sum(sizes) <= 64 * 10 ** 6
+    got_small = np.load(str(tmp_path / "a" / "small.npy"))
+    assert got_small.dtype == np.float32 and np.array_equal(got_small, small)
+    got = np.load(str(tmp_path / "a" / "reduce.npy"))
+    assert got.dtype == np.float32 and got.shape[1:] == big.shape[1:] and 1024 < got.shape[0] < 2048
+    rows = got[:, 0, 0]
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, big[rows.astype(np.int64)])  # whole rows, in order
+    assert np.array_equal(got, np.load(str(tmp_path / "b" / "reduce.npy")))  # the same rows on every run
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run: the result line with the standard keys and nothing measured beside them; --steps K times K steps;
+    --dump-outputs writes the reduced image of the last step, equal to the oracle's."""
+    import subprocess
+    import sys
+
+    from tests import helpers
+
+    out_dir = str(tmp_path / "dump")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--size", "2048", "--dump-outputs", out_dir]
+    proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=str(tmp_path),
+                          timeout=600)
+    assert proc.returncode == 0, proc.stderr[-2000:]
+    lines = proc.stdout.strip().splitlines()
+    assert not any(l.startswith("bench_full") for l in lines)
+    line = _strict_loads(lines[-1])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["roofline"] is None and line["parity"] is None and line["cpu_baseline"] is None
+    assert "full" not in line and not os.path.exists(os.path.join(str(tmp_path), "bench_full.json"))
+    got = np.load(os.path.join(out_dir, "reduce.npy"))
+    want = helpers.Port.reduce(helpers.lcg_image(2048, 2048, 4, np.uint8), 8, 8, "lanczos3")
+    assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32))

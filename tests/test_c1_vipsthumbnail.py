@@ -19,7 +19,7 @@ def run_cli(tmp_path, src, size):
     src_path = os.path.join(str(tmp_path), "src.v")
     out_path = os.path.join(str(tmp_path), "out.v")
     helpers.write_v(src_path, src, interpretation=22)
-    env = dict(os.environ, VIPS_INFO="1")
+    env = helpers.ref_cli_env(VIPS_INFO="1")
     proc = subprocess.run([VIPSTHUMBNAIL, src_path, "--size", size, "-o", out_path],
                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env, text=True)
     assert proc.returncode == 0, proc.stdout

@@ -251,7 +251,7 @@ def test_bench_programs_under_torchrun(config, extra):
     env = dict(os.environ, BENCH_FORCE_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(helpers.ROOT, "bench.py"), "--gpus", "1",
-           "--steps", "2", "--warmup", "1", "--config", config, "--no-cpu-baseline"] + extra
+           "--steps", "2", "--warmup", "1", "--config", config, "--full", "--no-cpu-baseline"] + extra
     proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
     assert proc.returncode == 0, proc.stderr[-2000:]
     line = json.loads(proc.stdout.strip().splitlines()[-1])

@@ -49,7 +49,7 @@ def test_header_of_a_reference_written_file(tmp_path, dtype, interp):
     a, b = str(tmp_path / "a.v"), str(tmp_path / "b.v")
     helpers.write_v(a, src, interpretation=interp)
     proc = subprocess.run([VIPS, "copy", a, b, "--xres", "3.5", "--xoffset", "7"], stdout=subprocess.PIPE,
-                          stderr=subprocess.STDOUT, text=True)
+                          stderr=subprocess.STDOUT, text=True, env=helpers.ref_cli_env())
     assert proc.returncode == 0, proc.stdout
     h = read_header(b)
     assert (h.width, h.height, h.bands, h.format, h.coding, h.interpretation) == \
@@ -61,7 +61,8 @@ def test_header_of_a_reference_written_file(tmp_path, dtype, interp):
     # the helper's writer (what the GPU round-trip test compares the product's files with) makes
     # the header the reference's own writer makes
     c = str(tmp_path / "c.v")
-    proc = subprocess.run([VIPS, "copy", a, c], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    proc = subprocess.run([VIPS, "copy", a, c], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                          env=helpers.ref_cli_env())
     assert proc.returncode == 0, proc.stdout
     assert open(c, "rb").read(64) == open(a, "rb").read(64)
 
@@ -140,10 +141,12 @@ def test_reference_reads_what_we_write(tmp_path):
     src = helpers.lcg_image(300, 200, 3, np.uint8, 96)
     path = str(tmp_path / "thumb.v")
     Image.new_from_array(src, interpretation="srgb").thumbnail_image(64).write_to_file(path)
-    proc = subprocess.run([VIPSHEADER, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    proc = subprocess.run([VIPSHEADER, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                          env=helpers.ref_cli_env())
     assert proc.returncode == 0 and "64x43 uchar, 3 bands, srgb" in proc.stdout, proc.stdout
     out = str(tmp_path / "inv.v")
-    proc = subprocess.run([VIPS, "invert", path, out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    proc = subprocess.run([VIPS, "invert", path, out], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                          env=helpers.ref_cli_env())
     assert proc.returncode == 0, proc.stdout
     ours, _ = helpers.read_v(path)
     inv, _ = helpers.read_v(out)

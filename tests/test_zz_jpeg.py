@@ -143,7 +143,7 @@ def test_truncated_file_decodes_like_the_reference(tmp_path):
 
 def cli_thumbnail(tmp_path, src, size, extra=()):
     out_path = os.path.join(str(tmp_path), "cli_out.v")
-    env = dict(os.environ, VIPS_INFO="1")
+    env = helpers.ref_cli_env(VIPS_INFO="1")
     proc = subprocess.run([VIPSTHUMBNAIL, src, "--size", size, "-o", out_path] + list(extra),
                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=env, text=True)
     assert proc.returncode == 0, proc.stdout
