@@ -583,13 +583,17 @@ struct MfmaStep {
 		}
 	}
 
-	// hwalk that also hands out the UNROUNDED sums of the segment's outputs 0, 1, 2 (raw[0..2]) and 5, 6, 7
-	// (raw[3..5]): the exchange kernel's partial sums of the outputs that straddle a tile boundary
+	// The exchange kernel's walk: a segment of 9 outputs (eight segments cover the tile's 64 outputs and
+	// the three either side that straddle its boundaries, -3 .. 68, in ONE pass of the whole block).  Output O of
+	// the segment uses slot O mod 8 from group O on: output 8 takes slot 0 after output 0 has retired, the table's
+	// zero taps (d = 6, 7) keep the slot clear in between.  Lane hc keeps outputs 2 hc, 2 hc + 1 (pix[0], pix[1]),
+	// lane 0 output 8 as well (pix[2]); every lane hands out the UNROUNDED sums of its channel's outputs 0 .. 6
+	// (raw): the partial sums of the straddling outputs.
 	template <int G>
 	static __device__ __forceinline__ void hwalk_x(float4v (&hacc)[2], const unsigned char *line, const half4v *lane_ah,
-		int hc, unsigned int (&pix)[2], float (&raw)[6])
+		int hc, unsigned int (&pix)[3], float (&raw)[7])
 	{
-		constexpr int NG = HSEG_OUT + D - 1;
+		constexpr int NG = 9 + D - 1;
 		if constexpr (G < NG) {
 			constexpr int ROT = G % MFMA_SLOTS;
 			const half4v b0 = bytes_b(*reinterpret_cast<const unsigned int *>(line + 8 * G));
@@ -602,15 +606,13 @@ struct MfmaStep {
 			constexpr int H = SLOT >> 2, I = SLOT & 3;
 			if constexpr (G >= D - 1) {
 				constexpr int O = G - (D - 1);
-				if constexpr (O < 3)
+				if constexpr (O < 7)
 					raw[O] = hacc[H][I];
-				if constexpr (O >= 5)
-					raw[O - 2] = hacc[H][I];
 				int v = (int) fin_pack(hacc[H][I], (unsigned int) hc, 0);
 				v |= __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true); // quad_perm [1,0,3,2]
 				v |= __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true); // quad_perm [2,3,0,1]
-				if (hc == O / 2)
-					pix[O & 1] = (unsigned int) v;
+				if (hc == (O / 2 & 3))
+					pix[O / 2 == 4 ? 2 : O & 1] = (unsigned int) v;
 			}
 			hacc[H][I] = 0.0f;
 			if constexpr ((G & 1) == 1)
@@ -812,7 +814,10 @@ reduce_fused_u8x4_mfma(FusedArgs a, const MfmaTables *__restrict__ tables)
 // vertical halo) against 1.22 x.
 constexpr int XH = 48;                 // halo bytes either side of a T plane row
 constexpr int XPLANE = XH + 512 + XH + 4; // 612 bytes = 153 dwords (odd: 32 planes in 32 banks)
-constexpr int XGUARD = 64;             // in front of the planes: segment -1 of plane 0 reads 40 bytes before its row
+// (the horizontal walk's segment 0 starts 8 * 3 - fx0 <= 48 bytes before a plane row's column 0: inside the halo.  Its
+// segment 7 reads up to byte 591 + fx0 <= 575 of the row, past the 48-byte halo into the next plane row -- or, for
+// the last plane, the tap tables: harmless, only the discarded outputs 67 / 68 and zero taps (d = 6, 7) read them)
+constexpr int XGUARD = 64;             // in front of the planes
 constexpr int XPLANES_BYTES = XGUARD + MFMA_SLOTS * 4 * XPLANE;
 constexpr int XPART = 48;              // floats per row: [side 2][straddling output 6][channel 4]
 constexpr int XMAX_OHT = 128;
@@ -821,13 +826,18 @@ static constexpr size_t xlds_bytes(int oht)
 	return (size_t) XPLANES_BYTES + 2 * MFMA_TABLE_ENTRIES * 8 + (size_t) oht * 64 * 4 + (size_t) oht * XPART * 4;
 }
 
-template <int D, int NB, int OCC>
-__global__ void __launch_bounds__(FUSED_THREADS, OCC)
-reduce_fused_u8x4_mfma_x(FusedArgs a, const MfmaTables *__restrict__ tables, float *parts, int *arrivals, int plain,
-	int *misplaced)
+// Profiling builds of the exchange kernel (PROF bits; the shipped kernel is PROF = 0, reduce_exch_prof the others,
+// reached only through $VIPS_HIP_FUSED_DEBUG): the load stream alone (no arithmetic, no horizontal pass, no tile end),
+// no horizontal pass, no tile end; every row fetched with the default cache policy instead of `nt` (XPROF_L2: what the
+// halo rows -- read by both tiles of a row boundary, at about the same time -- can gain from the L2, as a bound)
+constexpr int XPROF_LOADS = 1, XPROF_NO_H = 2, XPROF_NO_END = 4, XPROF_L2 = 8;
+
+template <int D, int NB, int PROF>
+__device__ __forceinline__ void reduce_fused_x_body(const FusedArgs &a, const MfmaTables *__restrict__ tables,
+	float *parts, int *arrivals, int plain, int *misplaced)
 {
 	constexpr int S = 8;
-	typedef MfmaStep<D, true, 0, true, FUSED_THREADS, 1, XPLANE> Step;
+	typedef MfmaStep<D, !(PROF & XPROF_L2), (PROF & XPROF_LOADS) ? 16 : 0, true, FUSED_THREADS, 1, XPLANE> Step;
 	VH_DYNAMIC_LDS(unsigned char, lds_raw);
 	unsigned char *planes = lds_raw + XGUARD + XH; // byte p of a plane row = the tile's own column p
 	half4v *lds_a = reinterpret_cast<half4v *>(lds_raw + XPLANES_BYTES);
@@ -899,54 +909,50 @@ reduce_fused_u8x4_mfma_x(FusedArgs a, const MfmaTables *__restrict__ tables, flo
 		}
 		const int nrows = jhi - jlo + 1;
 		const int r_lo = jlo - (g0 - (D - 1));
-		// thread -> (T row, segment of HSEG_OUT outputs, channel); then the first wave again for the two
-		// segments outside the tile (outputs -8 .. -1 and 64 .. 71: the neighbours' straddling outputs)
-#pragma unroll 1
-		for (int round = 0; round < 2; round++) {
-			if (round == 1 && t >= 64)
-				break;
-			const int hc = t & 3, hr = (t >> 2) & 7;
-			const int hseg = round == 0 ? t >> 5 : ((t >> 5) & 1 ? 8 : -1);
+		if (!(PROF & (XPROF_LOADS | XPROF_NO_H))) {
+			// thread -> (T row, segment of 9 outputs, channel): segment s makes local outputs 9 s - 3 .. 9 s + 5, the
+			// eight of them every output of the tile and the neighbours' three straddling ones either side
+			const int hc = t & 3, hr = (t >> 2) & 7, hseg = t >> 5;
 			const half4v *lane_ah = lds_ah + hc;
 			const bool row_ok = hr < nrows;
 			const int lrow = r_lo + (row_ok ? hr : 0);
-			const unsigned char *line = planes + (lrow * 4 + hc) * XPLANE + a.fx0 + 8 * HSEG_OUT * hseg;
+			const int xs = 9 * hseg - 3; // the segment's first local output
+			const unsigned char *line = planes + (lrow * 4 + hc) * XPLANE + a.fx0 + 8 * xs;
 			float4v hacc[2];
 			hacc[0] = (float4v){ 0.0f, 0.0f, 0.0f, 0.0f };
 			hacc[1] = (float4v){ 0.0f, 0.0f, 0.0f, 0.0f };
-			unsigned int pix[2] = { 0, 0 };
-			float raw[6];
+			unsigned int pix[3] = { 0, 0, 0 };
+			float raw[7];
 			Step::template hwalk_x<0>(hacc, line, lane_ah, hc, pix, raw);
-			if (!row_ok)
-				continue;
-			const int jj = jlo + hr;
-			if (round == 0)
-				*reinterpret_cast<uint2 *>(stage + jj * 64 + HSEG_OUT * hseg + 2 * hc) = make_uint2(pix[0], pix[1]);
-			// straddling outputs, side 0: local outputs -3 .. 2, side 1: 61 .. 66
-			float *prow = part + jj * XPART + hc;
-			if (hseg == 0) {
+			if (row_ok) {
+				const int jj = jlo + hr;
+				unsigned int *srow = stage + jj * 64;
+				const int x = xs + 2 * hc; // pix[0], pix[1]: outputs x, x + 1; pix[2] (lane 0): output xs + 8
+				if (x >= 0 && x < 64)
+					srow[x] = pix[0];
+				if (x + 1 >= 0 && x + 1 < 64)
+					srow[x + 1] = pix[1];
+				if (hc == 0 && xs + 8 < 64)
+					srow[xs + 8] = pix[2];
+				// straddling outputs, side 0: local outputs -3 .. 2 (segment 0's 0 .. 5), side 1: 61 .. 66 (segment
+				// 7's 1 .. 6)
+				float *prow = part + jj * XPART + hc;
+				if (hseg == 0) {
 #pragma unroll
-				for (int o = 0; o < 3; o++)
-					prow[(3 + o) * 4] = raw[o];
-			}
-			else if (hseg == 7) {
+					for (int o = 0; o < 6; o++)
+						prow[o * 4] = raw[o];
+				}
+				else if (hseg == 7) {
 #pragma unroll
-				for (int o = 0; o < 3; o++)
-					prow[24 + o * 4] = raw[3 + o];
-			}
-			else if (hseg == -1) {
-#pragma unroll
-				for (int o = 0; o < 3; o++)
-					prow[o * 4] = raw[3 + o];
-			}
-			else if (hseg == 8) {
-#pragma unroll
-				for (int o = 0; o < 3; o++)
-					prow[24 + (3 + o) * 4] = raw[o];
+					for (int o = 0; o < 6; o++)
+						prow[24 + o * 4] = raw[1 + o];
+				}
 			}
 		}
 		__syncthreads();
 	}
+	if (PROF & (XPROF_LOADS | XPROF_NO_END))
+		return;
 
 	// ---- the tile's end.  Its partial sums leave first (write-through); then it ARRIVES at its two boundaries (an
 	// atomic counter each: two arrivals a launch, so the parity of what the atomic returns says who is second, launch
@@ -1052,6 +1058,22 @@ reduce_fused_u8x4_mfma_x(FusedArgs a, const MfmaTables *__restrict__ tables, flo
 			}
 		}
 	}
+}
+
+template <int D, int NB, int OCC>
+__global__ void __launch_bounds__(FUSED_THREADS, OCC)
+reduce_fused_u8x4_mfma_x(FusedArgs a, const MfmaTables *__restrict__ tables, float *parts, int *arrivals, int plain,
+	int *misplaced)
+{
+	reduce_fused_x_body<D, NB, 0>(a, tables, parts, arrivals, plain, misplaced);
+}
+
+template <int D, int NB, int OCC, int PROF>
+__global__ void __launch_bounds__(FUSED_THREADS, OCC)
+reduce_exch_prof(FusedArgs a, const MfmaTables *__restrict__ tables, float *parts, int *arrivals, int plain,
+	int *misplaced)
+{
+	reduce_fused_x_body<D, NB, PROF>(a, tables, parts, arrivals, plain, misplaced);
 }
 
 // The straddling outputs: boundary k (0 .. tiles_x: 0 and tiles_x are the image's edges, where one tile holds the
@@ -1929,16 +1951,27 @@ static int launch_fused_mfma_x(const FusedArgs &all, const VipsHipRegion *in, co
 	const size_t lds = xlds_bytes(a.oht);
 	const int rows_per_xcd = (tiles_y + 7) / 8;
 	const int grid = 8 * rows_per_xcd * a.tiles_x; // (the kernel's numbering: XCD k takes rows k rows_per_xcd ...)
+	// $VIPS_HIP_FUSED_DEBUG bits 64 / 128 / 256: the profiling builds (XPROF_LOADS / NO_H / NO_END; their output is
+	// not the image's), 512: XPROF_L2 (output unchanged).  (NB = 2 and 1 were measured too, 3-4 % slower than 4:
+	// profiles/NOTES.md R7.1)
+	typedef void (*XKernel)(FusedArgs, const MfmaTables *, float *, int *, int, int *);
+	XKernel kern = reduce_fused_u8x4_mfma_x<6, 4, 2>;
+	switch ((a.debug >> 6) & 15) {
+	case XPROF_LOADS: kern = reduce_exch_prof<6, 4, 2, XPROF_LOADS>; break;
+	case XPROF_NO_H: kern = reduce_exch_prof<6, 4, 2, XPROF_NO_H>; break;
+	case XPROF_NO_END: kern = reduce_exch_prof<6, 4, 2, XPROF_NO_END>; break;
+	case XPROF_L2: kern = reduce_exch_prof<6, 4, 2, XPROF_L2>; break;
+	default: break;
+	}
 	int rc = 0;
 	{
 		Gate gate("reduce_fused_u8_mfma_x");
 		hipError_t err;
 		{
-			err = hipFuncSetAttribute((const void *) reduce_fused_u8x4_mfma_x<6, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-				80 * 1024);
+			err = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
 			if (err == hipSuccess)
-				hipLaunchKernelGGL((reduce_fused_u8x4_mfma_x<6, 4, 2>), dim3(grid), dim3(FUSED_THREADS), lds, stream(), a, d_tables,
-					parts, arrivals, plain, misplaced);
+				hipLaunchKernelGGL(kern, dim3(grid), dim3(FUSED_THREADS), lds, stream(), a, d_tables, parts, arrivals, plain,
+					misplaced);
 		}
 		if (err != hipSuccess || hipGetLastError() != hipSuccess)
 			rc = -1;
