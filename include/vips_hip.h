@@ -421,6 +421,13 @@ typedef enum {
 	VIPS_HIP_COLOUR_Lab2LabS,       /* Lab2LabS.c:59-73 */
 	VIPS_HIP_COLOUR_LabS2Lab,       /* LabS2Lab.c:55-69 */
 	VIPS_HIP_COLOUR_sRGB2scRGB16,   /* sRGB2scRGB.c:91-105, RGB16 (ushort) in */
+	/* greyscale and 16-bit RGB: the band count or the band format of the WHOLE pel changes */
+	VIPS_HIP_COLOUR_scRGB2BW,       /* scRGB2BW.c:59-105 depth 8: float x 3 in, uchar x 1 out */
+	VIPS_HIP_COLOUR_scRGB2BW16,     /* scRGB2BW.c, depth 16: ushort x 1 out */
+	VIPS_HIP_COLOUR_BW2sRGB,        /* colourspace.c:152-175: the band three times, any format */
+	VIPS_HIP_COLOUR_GREY162RGB16,   /* colourspace.c:177-186: the same, tagged RGB16 */
+	VIPS_HIP_COLOUR_sRGB2RGB16,     /* colourspace.c:99-109: shift cast of every band to ushort */
+	VIPS_HIP_COLOUR_RGB162sRGB,     /* colourspace.c:83-97: shift cast of every band to uchar */
 	VIPS_HIP_COLOUR_LAST
 } VipsHipColourStep;
 
@@ -433,6 +440,10 @@ VIPS_HIP_API int vips_hip_colour_gen(int step,
  * Lab2LabS) only last.  The stored input may be uchar, ushort, short or float: it is
  * vips_cast to what the first step wants (colour.c:343-348,428-434).  @alpha_scale is
  * max_alpha_after / max_alpha_before for the extra bands (colour.c:257-273).
+ * BW2sRGB / GREY162RGB16 may only come first (the input then has 1 colour band) and
+ * scRGB2BW* only last (the output then has 1); the two shift casts stand alone or
+ * straight behind a band-replicating step, act on every band and take no @alpha_scale.
+ * The extra bands are in->bands minus the input's colour bands, and as many in @out.
  */
 VIPS_HIP_API int vips_hip_colour_route_gen(const int *steps, int n_steps, double alpha_scale,
 	const VipsHipRegion *in, const VipsHipRegion *out);

@@ -18,6 +18,10 @@ int band_cast(const VipsHipRegion *in, int in_first, const VipsHipRegion *out, i
 int colour_route(const int *steps, int n_steps, double alpha_scale, const VipsHipRegion *in,
 	const VipsHipRegion *out);
 
+// B_W -> GREY16 (to16) or GREY16 -> B_W of a one-band uchar / ushort image: the route as a table made on the
+// device by the route's own steps, applied from LDS by one streaming kernel
+int grey_lut_image(const VipsHipRegion *in, const VipsHipRegion *out, bool to16);
+
 // vips_sharpen on a whole 3-band uchar sRGB image in one kernel (colour.hip); 1 = not its case
 // (win: the part of the LUT that is not constant, as shorts on the device -- the kernel with every table in LDS;
 // nullptr: the kernel that reads the whole LUT through global memory)

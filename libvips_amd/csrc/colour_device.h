@@ -234,6 +234,32 @@ static __device__ __forceinline__ int scRGB2sRGB_channel(const int *__restrict__
 	return vh::cvt_i32(rintf(r));
 }
 
+// vips_col_scRGB2BW, LabQ2sRGB.c:385-429: CIE luminance, every product and sum rounded on its own, then
+// the table lerp of one scRGB2sRGB channel
+static __device__ __forceinline__ int scRGB2BW_value(const int *__restrict__ lut, float R, float G, float B, int maxval)
+{
+	const float Y = __fadd_rn(__fadd_rn(__fmul_rn(0.2126F, R), __fmul_rn(0.7152F, G)), __fmul_rn(0.0722F, B));
+	if (isnan(Y))
+		return 0;
+	return scRGB2sRGB_channel(lut, Y, maxval);
+}
+
+// vips_cast with shift = TRUE between the two unsigned formats of the sRGB / RGB16 pair (cast.c:138-163):
+// widening copies the low bit into the fresh bits, narrowing drops the low byte (0 .. 255: nothing to clamp);
+// the same format is a copy.  Other pairs are refused on the host.
+template <typename TOUT, typename TIN>
+static __device__ __forceinline__ TOUT shift_cast(TIN v)
+{
+	if constexpr (std::is_same<TIN, TOUT>::value)
+		return v;
+	else if constexpr (std::is_same<TIN, unsigned char>::value && std::is_same<TOUT, unsigned short>::value)
+		return (TOUT) (((unsigned int) v << 8) | ((((unsigned int) v & 1u) << 8) - ((unsigned int) v & 1u)));
+	else if constexpr (std::is_same<TIN, unsigned short>::value && std::is_same<TOUT, unsigned char>::value)
+		return (TOUT) ((unsigned int) v >> 8);
+	else
+		return (TOUT) 0;
+}
+
 // vips_Lab2LabS_line, Lab2LabS.c:59-73: double multiply, clip, truncate
 static __device__ __forceinline__ short lab2labs(float v, double scale, double lo)
 {
@@ -305,7 +331,8 @@ struct RouteArgs {
 	int in_bands, out_bands; // bands per pel in memory (3 colour + extra)
 	int n_steps;
 	int steps[8];
-	int extra_bands;      // bands carried through after the 3 colour bands
+	int extra_bands;      // bands carried through after the colour bands
+	int in_colour, out_colour; // colour bands of a stored pel: 3, or 1 on the grey side of a grey route
 	double alpha_scale;   // max_alpha_after / max_alpha_before (colour.c:257-273), 1.0 = none
 	ColourTables tables;
 };
@@ -509,6 +536,12 @@ static __device__ __forceinline__ void route_pixel(const RouteArgs &a, const flo
 		o0 = (TOUT) r;
 		o1 = (TOUT) g;
 		o2 = (TOUT) b;
+	}
+	else if (last == VIPS_HIP_COLOUR_scRGB2BW || last == VIPS_HIP_COLOUR_scRGB2BW16) {
+		// one band: the caller stores o0 (out_colour = 1)
+		const int g = last == VIPS_HIP_COLOUR_scRGB2BW16 ? scRGB2BW_value(a.tables.Y2v_16, v.a, v.b, v.c, 65535)
+														 : scRGB2BW_value(Y2v8, v.a, v.b, v.c, 255);
+		o0 = o1 = o2 = (TOUT) g;
 	}
 	else if (last == VIPS_HIP_COLOUR_Lab2LabS) {
 		o0 = (TOUT) lab2labs(v.a, 32767.0 / 100.0, 0.0);
