@@ -5,7 +5,7 @@
 // instructions per output byte at half rate (0.4 - 0.75 ms for 8192^2 x 3, 6 - 13 % of HBM); as
 // v_mfma_f32_32x32x16_f16 it is 8 matrix instructions per 1024 output bytes.
 //
-// Exact integers in f32, as in reduce_u8.hip: a pixel byte p is the f16 DENORMAL 0x00pp = p 2^-24 (no
+// Exact integers in f32, as in reduce_u8_device.h: a pixel byte p is the f16 DENORMAL 0x00pp = p 2^-24 (no
 // conversion: a v_perm puts a zero byte above it), a coefficient |c| < 2048 is an exact half, every product
 // and every partial sum is an integer below 2^24 times 2^-24.  Rounding as in conv_u8_body.h: clip(floor((S +
 // scale / 2) / scale)) = RNE(S RN(1 / scale) + bias) saturated to 0 .. 255, bias = -0.5 + 1 / (2 scale) + (scale / 2)

@@ -1,5 +1,5 @@
 // The few statements with no C++ spelling that whole kernel FILES (convsep_stream.hip, convsep_f32.hip,
-// reduce_u8.hip ...) are written with -- register-class hints, s_waitcnt, the LDS-DMA, dynamic LDS -- under
+// reduce_fused_u8.hip ...) are written with -- register-class hints, s_waitcnt, the LDS-DMA, dynamic LDS -- under
 // names, so that the same files also compile for host fibers: tests/emul/kernel_prelude.h gives the names host
 // meanings (and defines this header's guard), the product gets the instructions.
 #ifndef VH_KERNEL_STMT_H

@@ -3,7 +3,7 @@
 // on the matrix cores: out = A x in with A the banded matrix that holds, for output row y, the n_point
 // coefficients cy[ty(y)][k] at input rows iy(y) + k -- a GEMM whose left matrix is made on the host.
 //
-// Exact integers in f32 as in reduce_u8.hip / conv_u8_mfma_body.h: a byte is the f16 denormal 0x00pp, a
+// Exact integers in f32 as in reduce_u8_device.h / conv_u8_mfma_body.h: a byte is the f16 denormal 0x00pp, a
 // coefficient |c| < 2048 an exact half, sums below 2^24; retire = fma(acc, 4096, 2^-13) + v_cvt_pk_u8_f32 =
 // clip((S + 2048) >> 12) (templates.h:152-157).
 //

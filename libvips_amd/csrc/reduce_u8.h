@@ -11,7 +11,9 @@
 
 namespace vh {
 
+// reduce_fused_u8x3.hip: vips_reduceh by 8 on three interleaved bands, on the matrix cores
 int reduceh_u8x3_try(const _VipsHipReduce *r, const VipsHipRegion *in, const VipsHipRegion *out, int tile);
+// reducev_u8.hip
 int reducev_u8_try(const _VipsHipReduce *r, const VipsHipRegion *in, const VipsHipRegion *out,
 	const ReducePos *pos, const short *table, int tile);
 int shrinkv_u8_try(int vshrink, const VipsHipRegion *in, const VipsHipRegion *out);

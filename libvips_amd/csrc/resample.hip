@@ -5,7 +5,7 @@
 //     thread per output element, taps fetched with edge clamping.  They define
 //     correctness for the whole format matrix of reduceh.cpp:278-322 /
 //     reducev.cpp:563-609 / shrinkh.c:175-232 / shrinkv.c:181-310.
-//   * uchar fast kernels (reduce_u8.hip): LDS-staged, wave-coalesced kernels for
+//   * uchar fast kernels (reducev_u8.hip, reduce_fused_u8x3.hip): LDS-staged, wave-coalesced kernels for
 //     the 8-bit paths the reference vectorises with Highway
 //     (reduceh_hwy.cpp:79, reducev_hwy.cpp:94, shrinkh_hwy.cpp:68,
 //     shrinkv_hwy.cpp:90,133), selected here when the geometry allows.

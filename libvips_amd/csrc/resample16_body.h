@@ -190,7 +190,7 @@ static __device__ __forceinline__ void shrinkv16_body(const R16VArgs &a, int bx,
 // extended: v_perm), every output row in flight takes its two taps from it with one
 // v_dot2_i32_i16.  Sums start at 2048 (templates.h:152-157's rounding term; no bias: a byte is a
 // non-negative 16-bit value), retire as clip(sum >> 12) to 0 .. 255.  reducev_u8_kernel
-// (reduce_u8.hip) gives a thread one output row and re-reads its n_point input rows through L2.
+// (reducev_u8.hip) gives a thread one output row and re-reads its n_point input rows through L2.
 static __device__ __forceinline__ void reducev8_body(const R16VArgs &a, int item)
 {
 	const int t = tid();

@@ -79,7 +79,7 @@ static __device__ __forceinline__ int rs_dot2(unsigned int pix, unsigned int coe
 	return __builtin_amdgcn_sdot2(__builtin_bit_cast(rs_short2, pix), __builtin_bit_cast(rs_short2, coef), acc, false);
 }
 
-// (sum + 2048) >> 12, clip (templates.h:152-157); see fin_u8 in reduce_u8.hip for the asm
+// (sum + 2048) >> 12, clip (templates.h:152-157); see fin_u8 in reduce_u8_device.h for the asm
 static __device__ __forceinline__ unsigned int rs_fin(int s)
 {
 	s = (s + (INTERPOLATE_SCALE >> 1)) >> INTERPOLATE_SHIFT;
@@ -253,7 +253,7 @@ resize_stream_u8(StreamArgs a, StreamPtrs ptrs_by_value)
 	// HF: output rows wait in LDS and leave `burst` slabs at a time -- a trickle of small writes
 	// into the streaming read costs a fifth of its rate on this part (the stores of 1.5 % of the
 	// bytes: 0.0404 -> 0.0337 ms per image without them), a burst now and then far less (the same
-	// finding as reduce_u8.hip's output stage)
+	// finding as reduce_fused_u8.hip's output stage)
 	//
 	// ... and the bursts of ALL blocks fall together: a block writes what it holds when the chip-wide
 	// 100 MHz clock (s_memrealtime) crosses a multiple of 2^window ticks (and when its stage is

@@ -68,7 +68,7 @@ static __device__ __forceinline__ void tail_dma_dword(const unsigned char *src, 
 }
 
 // (sum + 2048) >> 12, clip (templates.h:152-157).  The shifted value is made opaque before the
-// clip for the reason given at fin_u8 in reduce_u8.hip (v_ashr_pk_u8_i32 keeps the upper half of
+// clip for the reason given at fin_u8 in reduce_u8_device.h (v_ashr_pk_u8_i32 keeps the upper half of
 // its destination on gfx950, the compiler assumes it is zeroed; tests/test_abi.py checks the
 // library for the instruction).
 static __device__ __forceinline__ unsigned int tail_fin(int s)

@@ -60,7 +60,7 @@ CASES = [
     # rows of whole dwords that are not whole 128-byte strips / 8-byte groups; a tall image (many blocks)
     (516, 333, 3, 7.3, "lanczos3", S), (100, 1500, 1, 4.3, "lanczos3", S), (44, 90, 3, 2.2, "lanczos3", S),
     # a shrink whose coefficients are not exact halves (>= 2048): the vector-ALU kernel; a constant phase: the
-    # matrix-core kernel of reduce_u8.hip
+    # matrix-core kernel of reducev_u8.hip
     (2104, 90, 4, 1.6, "lanczos3", "reducev_u8_stream"), (512, 512, 4, 8.0, "lanczos3", "reducev_u8_mfma"),
 ]
 

@@ -77,7 +77,7 @@ def test_reducev8_short_segments(tmp_path):
 
 
 def test_reducev8_matrix_core_rows_of_tiles(tmp_path):
-    """reducev_u8_mfma (reduce_u8.hip) on images of several rows of tiles: every other row is walked bottom-up
+    """reducev_u8_mfma (reducev_u8.hip) on images of several rows of tiles: every other row is walked bottom-up
     (the flipped problem, taps reversed), and with VIPS_HIP_BAND_NO_ALTERNATE=1 all of them top-down."""
     m = "reducev_u8_mfma"
     cases = [(600, 1300, 3, 8.0, "lanczos3", m), (512, 523, 4, 8.0, "lanczos3", m), (1000, 2000, 1, 8.0, "lanczos3", m),

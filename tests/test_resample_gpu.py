@@ -235,7 +235,7 @@ def test_c2_full_size():
 @pytest.mark.parametrize("shrink", [2, 4, 8])
 @pytest.mark.parametrize("size", [(1203, 917), (2048, 1024), (640, 8), (96, 2000)])
 def test_fused_reduce_rgba(shrink, size):
-    """The fused reducev+reduceh kernel (reduce_u8.hip): even integer shrink, RGBA uchar;
+    """The fused reducev+reduceh kernel (reduce_fused_u8.hip): even integer shrink, RGBA uchar;
     sizes that are / are not multiples of the shrink (phase 0 and constant non-zero
     phase), several tiles wide and tall, all four edges clamped."""
     from libvips_amd import lib

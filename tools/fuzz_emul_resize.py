@@ -1,5 +1,5 @@
-"""Random cases of the reduce / resize kernels on host fibers (tests/emul: reduce_u8.hip with its matrix instruction,
-resize_stream / resize_streamg / resize_tail, the general kernels -- the kernel files themselves under the mock HIP
+"""Random cases of the reduce / resize kernels on host fibers (tests/emul: reduce_fused_*.hip and reducev_u8.hip with
+their matrix instruction, resize_stream / resize_streamg / resize_tail, the general kernels -- the kernel files themselves under the mock HIP
 runtime): vips_reduce by integer and fractional factors, vips_resize by one or two scales, 1-4 bands, uchar --
 against the plain-C port, bit for bit.
   usage: LD_PRELOAD=tests/mock_hip/_build/libmockhip.so VIPS_HIP_LIBRARY=tests/emul/_build/libvipship_emul.so \

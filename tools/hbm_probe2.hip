@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(WAVES * 64) strip_ldsdma(const unsigned char *
 
 // ---- the fused reduce's exact tile geometry: tiles_x x tiles_y tiles, tile (bx, by) reads `rows`
 // rows from row by * row_pitch and SW bytes from byte column bx * col_pitch; XCD-contiguous tile
-// ranges and the serpentine walk as in reduce_u8.hip.  `lds_pad` bytes of dynamic LDS bound
+// ranges and the serpentine walk as in reduce_fused_u8.hip.  `lds_pad` bytes of dynamic LDS bound
 // the blocks per CU like the real kernel's planes / stage do.
 struct TileGeo {
 	int tiles_x, tiles_y, rows, row_pitch, col_pitch;

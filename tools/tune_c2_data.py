@@ -25,7 +25,8 @@ with torch.cuda.stream(stream):
     }
 torch.cuda.synchronize()
 ims = {k: Image.new_from_tensor(v) for k, v in data.items()}
-knobs = [("full", {}), ("loads_only", {"VIPS_HIP_FUSED_DEBUG": "16"}), ("arith_only", {"VIPS_HIP_FUSED_DEBUG": "8"})]
+# (64: the exchange kernel's loads-only profiling build, reduce_exch_prof)
+knobs = [("full", {}), ("loads_only", {"VIPS_HIP_FUSED_DEBUG": "64"})]
 times = {}
 with torch.cuda.stream(stream):
     for rnd in range(5):

@@ -37,10 +37,9 @@ def main():
                 write = kb
     if fetch is None or write is None:
         raise SystemExit("no FETCH_SIZE / WRITE_SIZE rows for reduce_fused_u8x4_mfma in %s" % path)
-    src = "libvips_amd/csrc/reduce_u8.hip"
-    # the instantiation C2 launches: reduce_fused_u8x4_mfma_x<6, 4, 2> (before round 6:
-    # reduce_fused_u8x4_mfma<6, 1, 4, true, 0, true, 256, 1>)
-    symbol = "reduce_fused_u8x4_mfma_xILi6ELi4ELi2EE" if exchange else "reduce_fused_u8x4_mfmaILi6ELi1ELi4ELb1ELi0ELb1ELi256ELi1EE"
+    src = "libvips_amd/csrc/reduce_fused_exch.hip" if exchange else "libvips_amd/csrc/reduce_fused_u8.hip"
+    # the instantiation C2 launches: reduce_fused_u8x4_mfma_x<6, 4, 2> (before round 6: reduce_fused_u8x4_mfma<6>)
+    symbol = "reduce_fused_u8x4_mfma_xILi6ELi4ELi2EE" if exchange else "reduce_fused_u8x4_mfmaILi6EE"
     sha = kernel_isa_sha(symbol)
     if sha is None:
         raise SystemExit("libvipship.so holds no gfx950 function named *%s*" % symbol)
