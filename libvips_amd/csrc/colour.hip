@@ -2746,7 +2746,7 @@ int colour_route(const int *steps, int n_steps, double alpha_scale, const VipsHi
 
 	dim3 block(256, 1, 1);
 	dim3 grid((a.width + 255) / 256, rows_grid((a.width + 255) / 256, a.height), 1);
-	Gate gate("colour_route");
+	// (a gate name per kernel family, given where the launch is chosen: a report says which one ran)
 	// 3 bands in and out, rows that start and advance on 4-element boundaries: 4 pixels per thread
 	const int oes = format_sizeof(want_out);
 	const bool x4 = in->bands == 3 && out->bands == 3 && !(a.width & 3) &&
@@ -2767,6 +2767,7 @@ int colour_route(const int *steps, int n_steps, double alpha_scale, const VipsHi
 		const CbrtQuad *cq = cbrt_quad_tables();
 		const CbrtExact *cx = cq ? nullptr : cbrt_exact_tables();
 		if (cq) {
+			Gate gate("colour_lab_quad");
 			const int gx = (a.width / 4 + 1023) / 1024;
 			int gy = (256 + gx - 1) / gx; // one block of 1024 per CU, each walking its share of the rows
 			const char *e = getenv("VIPS_HIP_LAB_QUAD_GRID");
@@ -2785,6 +2786,7 @@ int colour_route(const int *steps, int n_steps, double alpha_scale, const VipsHi
 			launched = true;
 		}
 		else if (cx) {
+			Gate gate("colour_lab_lds");
 			const int gx = (a.width / 4 + 255) / 256;
 			int gy = (256 * 4 + gx - 1) / gx; // four 34 KB blocks per CU, each walking its share of the rows
 			gy = gy > a.height ? a.height : gy;
@@ -2813,6 +2815,7 @@ int colour_route(const int *steps, int n_steps, double alpha_scale, const VipsHi
 	}
 #define STATIC_ROUTE(R, TIN, FIN, TOUT, FOUT) \
 	if (!launched && route_id == R && in->format == FIN && want_out == FOUT) { \
+		Gate gate("colour_route_x4_static"); \
 		hipLaunchKernelGGL((colour_route_x4_kernel<TIN, TOUT, R>), grid4, block, 0, stream(), a); \
 		launched = true; \
 	}
@@ -2826,10 +2829,14 @@ int colour_route(const int *steps, int n_steps, double alpha_scale, const VipsHi
 #define GO(TIN, TOUT) \
 	if (launched) \
 		; \
-	else if (x4) \
+	else if (x4) { \
+		Gate gate("colour_route_x4"); \
 		hipLaunchKernelGGL((colour_route_x4_kernel<TIN, TOUT, 0>), grid4, block, 0, stream(), a); \
-	else \
-		hipLaunchKernelGGL((colour_route_kernel<TIN, TOUT>), grid, block, 0, stream(), a)
+	} \
+	else { \
+		Gate gate("colour_route"); \
+		hipLaunchKernelGGL((colour_route_kernel<TIN, TOUT>), grid, block, 0, stream(), a); \
+	}
 #define GO_IN(TOUT) \
 	switch (in->format) { \
 	case VIPS_HIP_FORMAT_UCHAR: GO(unsigned char, TOUT); break; \

@@ -916,9 +916,15 @@ int vips_hip_colourspace(VipsHipImage *in, VipsHipImage **out, int space)
 	VipsHipImage *cur = in;
 	const bool readable = cur->format == VIPS_HIP_FORMAT_UCHAR || cur->format == VIPS_HIP_FORMAT_USHORT ||
 		cur->format == VIPS_HIP_FORMAT_SHORT || cur->format == VIPS_HIP_FORMAT_FLOAT;
-	if (!readable) {
-		// (behind a band-replicating step the next step's cast: casting one band or its three copies is the same)
-		const int decode = step_replicates(first) ? (route->n > 1 ? steps[1] : -1) : first;
+	// (behind a band-replicating step the next step's cast: casting one band or its three copies is the same)
+	const int decode = step_replicates(first) ? (route->n > 1 ? steps[1] : -1) : first;
+	// The cast in front of a decoder narrows, and the reference casts the whole image, extra bands too, before it
+	// splits them off (a float sRGB image's alpha of 159.2 leaves vips_sRGB2scRGB as 159): the kernel applies the
+	// cast to the colour bands only, so an image with extra bands in another format than the decoder's is cast first.
+	const int narrow = decode == VIPS_HIP_COLOUR_sRGB2scRGB ? VIPS_HIP_FORMAT_UCHAR
+		: decode == VIPS_HIP_COLOUR_sRGB2scRGB16 ? VIPS_HIP_FORMAT_USHORT
+		: decode == VIPS_HIP_COLOUR_LabS2Lab ? VIPS_HIP_FORMAT_SHORT : -1;
+	if (!readable || (cur->bands > in_colour && narrow >= 0 && cur->format != narrow)) {
 		if (decode < 0) {
 			error("colourspace", "band format %d is outside the HIP path of this route", cur->format);
 			return -1;

@@ -651,7 +651,8 @@ class PortCC(object):
     def colour_step(cls, array, step, interp_in):
         fn, tin, tout, interp_out = cls._STEPS[step]
         a = Port._prep(array)
-        main = np.ascontiguousarray(cls.cast(a[:, :, :3], tin))  # code/transform build casts
+        a = cls.cast(a, tin)  # code/transform build casts: the whole image, extra bands too
+        main = np.ascontiguousarray(a[:, :, :3])
         h, w, _ = main.shape
         out3 = np.empty((h, w, 3), dtype=tout)
         getattr(cls.lib(), fn)(main.ctypes.data, h * w, out3.ctypes.data)

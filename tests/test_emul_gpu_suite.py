@@ -27,7 +27,8 @@ JOBS = {
     "test_c1_and_the_new_kernels_files_on_the_cpu": (["tests/test_c1_vipsthumbnail.py", "tests/test_convsep_int_gpu.py"], [], 38),
     "test_resample_file_on_the_cpu": (["tests/test_resample_gpu.py"],
                                       ["resize", "thumbnail", "c2_full", "c2_quarter", "mfma_variants", "region_windows", "any_bands"], 160),
-    "test_dispatch_fuzz_file_on_the_cpu": (["tests/test_fuzz_dispatch_gpu.py"], [], 5),
+    "test_dispatch_fuzz_file_on_the_cpu": (["tests/test_fuzz_dispatch_gpu.py"], [], 6),
+    "test_colour_routes_file_on_the_cpu": (["tests/test_colour_routes_gpu.py"], [], 176),
 }
 
 
@@ -75,5 +76,13 @@ def test_resample_file_on_the_cpu():
 
 def test_dispatch_fuzz_file_on_the_cpu():
     """tests/test_fuzz_dispatch_gpu.py: the seeded sweep over the dispatch guards of the streaming and matrix-core
-    kernels (round 5's conv_u8_mfma / reduce_band included: v_mfma_f32_32x32x16_f16 / 16x16x32 as wave meetings)."""
+    kernels (round 5's conv_u8_mfma / reduce_band included: v_mfma_f32_32x32x16_f16 / 16x16x32 as wave meetings),
+    and over the guard of the 4-pixels-per-lane colour route kernels."""
     _run("test_dispatch_fuzz_file_on_the_cpu")
+
+
+def test_colour_routes_file_on_the_cpu():
+    """tests/test_colour_routes_gpu.py, all of it: every route kernel of colour.hip against the reference on every
+    uchar colour and on the wide domains of the other sources, the tiers behind the default kernel in child
+    processes of their own, the layouts round the quad kernel's block, the region form."""
+    _run("test_colour_routes_file_on_the_cpu")

@@ -2,7 +2,8 @@
 (reduceh_u8_packed, shrinkh_u8_stream, conv_u8 / conv_u8_mfma, conv_u16, reducev_u8_stream, reduce_band,
 resample16): sizes round the dword / quad / 16-byte / strip / segment boundaries, 1 .. 4 bands, widths whose
 rows are NOT whole dwords (the fall-back must be taken and still match), fractional and integer factors, masks
-round the coefficient limits.  Whatever kernel the library picks, the result must equal the reference's (the
+round the coefficient limits; the colour kind walks the guard of the 4-pixels-per-lane colour route kernels (bands,
+width & 3, pointer and stride alignment in region form) over the pairs of vips_colourspace.  Whatever kernel the library picks, the result must equal the reference's (the
 compiled reference when present, else the port) bit for bit; the report must name a kernel.  The host-fiber fuzz
 of round 4 (tools/fuzz_emul.py) cannot see what only the device does: waitcnt, compiler traps, the LDS-DMA."""
 import random
@@ -33,6 +34,100 @@ def _reference(chain, src, port_call):
     if helpers.have_ref():
         return helpers.Ref.run_chain(chain, src)
     return port_call()
+
+
+# ---- the colour kind: the guard of the 4-pixels-per-lane route kernels (bands, width & 3, the alignment of the row
+# pointers and strides) over the supported pairs of vips_colourspace
+
+COLOUR_SPACES = ["b-w", "grey16", "rgb16", "srgb", "scrgb", "xyz", "lab", "labs"]
+COLOUR_PAIRS = [(a, b) for a in COLOUR_SPACES for b in COLOUR_SPACES
+                if not (a in ("b-w", "grey16") and b in ("xyz", "lab", "labs"))]
+assert len(COLOUR_PAIRS) == 58
+# (the routes with kernels of their own are drawn more often: two of them are the only way to a compiled-in route)
+COLOUR_FAST = [("srgb", "lab"), ("srgb", "labs"), ("labs", "srgb"), ("lab", "srgb")]
+COLOUR_STEP_NUMBERS = {"sRGB2scRGB": 0, "scRGB2XYZ": 1, "XYZ2Lab": 2, "Lab2XYZ": 3, "XYZ2scRGB": 4, "scRGB2sRGB": 5,
+                       "Lab2LabS": 7, "LabS2Lab": 8}
+COLOUR_GATES = ("colour_lab_quad", "colour_lab_lds", "colour_route_x4_static", "colour_route_x4", "colour_route")
+COLOUR_OUT = {"srgb": np.uint8, "labs": np.int16, "scrgb": np.float32, "xyz": np.float32, "lab": np.float32}
+
+
+class _Pixels(object):
+    def __init__(self, array):
+        self.array = array
+
+    def numpy(self):
+        return self.array
+
+
+def _colour_source(rng, a, w, h, extra, seed):
+    from tests import colour_domains as dom
+
+    if a in ("b-w", "grey16"):
+        return helpers.lcg_image(w, h, 1 + extra, np.uint8 if a == "b-w" else np.uint16, seed)
+    fmt = "u8"
+    if a == "srgb" and rng.random() < 0.4:
+        fmt = "f32"
+    return dom.layout_input(a, fmt, w, h, 3 + extra, seed)
+
+
+def _colour_reference(src, a, b):
+    if helpers.have_ref():
+        return helpers.Ref.run("colourspace", src, "space=" + b, helpers.INTERP[a])
+    return helpers.PortCC.colourspace(src, b, a)
+
+
+def _colour_case(rng, seed):
+    import ctypes
+
+    from libvips_amd import _ffi
+
+    region = rng.random() < 1.0 / 3
+    if region or not helpers.have_ref():
+        # region form takes the step list: the pairs with a fused 3-band route (the port's routes, when it referees)
+        a, b = rng.choice(sorted(helpers.PortCC._ROUTES) + 3 * COLOUR_FAST)
+    else:
+        # (a space to itself is a copy, or a plain cast: no colour kernel, nothing for the report to name)
+        a, b = rng.choice([p for p in COLOUR_PAIRS if p[0] != p[1]] + 3 * COLOUR_FAST)
+    if not region:
+        w, h = _size(rng, 4), _size(rng, 4, 300)
+        extra = rng.choice([0, 0, 0, 1, 2])
+        src = _colour_source(rng, a, w, h, extra, seed)
+        if src.dtype == np.float32 and a == "srgb" and b == "rgb16":
+            src = src.clip(0, 255).astype(np.uint8)  # (a shift cast of a float image is refused)
+        im = Image.new_from_array(src, interpretation=a)
+        return ("colour", a, b, w, h, src.shape[2], src.dtype.name), lambda: im.colourspace(b), \
+            lambda: _colour_reference(src, a, b)
+    # a window of an image as the input region, a rectangle of that window as the output: aligned or not
+    full_w, full_h = _size(rng, 24), _size(rng, 8, 200)
+    src = _colour_source(rng, a, full_w, full_h, 0, seed)
+    aligned = rng.random() < 0.5
+    pick = (lambda hi: 4 * rng.randrange(0, hi // 4 + 1)) if aligned else (lambda hi: rng.randrange(0, hi + 1))
+    x0 = pick(full_w // 4)
+    ww = max(4, full_w - x0 - pick(full_w // 4))
+    left = x0 + pick(ww // 3)
+    w = max(1, x0 + ww - left - pick(ww // 3))
+    if aligned:
+        ww, w = max(4, ww & ~3), max(4, w & ~3)
+        w = min(w, (x0 + ww - left) & ~3)
+    y0 = rng.randrange(0, full_h // 3 + 1)
+    wh = full_h - y0 - rng.randrange(0, full_h // 3 + 1)
+    top = y0 + rng.randrange(0, wh // 2 + 1)
+    h = max(1, y0 + wh - top - rng.randrange(0, wh // 3 + 1))
+    steps = [COLOUR_STEP_NUMBERS[s] for s in helpers.PortCC._ROUTES[(a, b)]]
+
+    def call():
+        win = Image.new_from_array(np.ascontiguousarray(src[y0:y0 + wh, x0:x0 + ww]))
+        rin = win.region()
+        rin.left, rin.top, rin.im_width, rin.im_height = x0, y0, full_w, full_h
+        out = Image.new_from_array(np.zeros((h, w, 3), COLOUR_OUT[b]))
+        rout = out.region()
+        rout.left, rout.top, rout.im_width, rout.im_height = left, top, full_w, full_h
+        arr = (ctypes.c_int * len(steps))(*steps)
+        _ffi.check(_ffi.lib.vips_hip_colour_route_gen(arr, len(steps), ctypes.c_double(1.0), ctypes.byref(rin),
+                                                      ctypes.byref(rout)))
+        return _Pixels(out.numpy())
+    return ("colour-region", a, b, full_w, full_h, (x0, y0, ww, wh), (left, top, w, h), src.dtype.name), call, \
+        lambda: np.ascontiguousarray(_colour_reference(src, a, b)[top:top + h, left:left + w])
 
 
 def _case(rng, kind):
@@ -150,6 +245,8 @@ def _case(rng, kind):
         im = Image.new_from_array(src)
         return (kind, w, h, bands, sigma), lambda: im.gaussblur(sigma), \
             lambda: _reference("gaussblur:sigma=%r" % sigma, src, lambda: helpers.PortCC.gaussblur(src, sigma))
+    if kind == "colour":
+        return _colour_case(rng, seed)
     # a small 2-D mask on uchar / ushort
     w, h = _size(rng, 8), _size(rng, 8)
     dt = rng.choice([np.uint8, np.uint16])
@@ -170,7 +267,8 @@ def _case(rng, kind):
 
 @pytest.mark.parametrize("kind,count,seed", [("reduce", 60, 501), ("shrink", 30, 502), ("blur", 40, 503),
                                              ("convsep", 30, 504), ("conv", 30, 505), ("resize", 14, 506),
-                                             ("float", 40, 507), ("upsize", 24, 508), ("blur16", 24, 509)])
+                                             ("float", 40, 507), ("upsize", 24, 508), ("blur16", 24, 509),
+                                             ("colour", 90, 510)])
 def test_fuzz_dispatch(kind, count, seed):
     rng = random.Random(seed)
     lib = libvips_amd.lib
@@ -190,9 +288,19 @@ def test_fuzz_dispatch(kind, count, seed):
             kernels[k] = kernels.get(k, 0) + 1
         want = ref()
         assert got.shape == want.shape and got.dtype == want.dtype, (desc, got.shape, want.shape)
+        if kind == "colour":
+            # the rule of tests/test_colour_routes_gpu.py: bytes equal, but that NaN on both sides counts as equal
+            from tests import colour_domains
+
+            bad = colour_domains.differing(got, want)
+            assert len(bad) == 0, (desc, dict(report), len(bad), bad[:4].tolist())
+            continue
         if got.dtype == np.float32:  # (bit for bit, NaN-safe: the float paths are the reference's operations in its order)
             got, want = got.view(np.int32), want.view(np.int32)
         bad = np.argwhere(got != want)
         assert len(bad) == 0, (desc, dict(report), len(bad), bad[:4].tolist())
     # the sweep must have reached the fast kernels AND their fall-backs
     assert len(kernels) >= {"upsize": 1, "blur16": 2}.get(kind, 3), kernels
+    if kind == "colour":
+        # four of the five families of colour_route() (the fifth, colour_lab_lds, needs another cube-root table)
+        assert len([k for k in COLOUR_GATES if k in kernels]) >= 4, kernels

@@ -155,3 +155,35 @@ def test_srgb_labs_srgb_is_the_identity_on_every_colour():
     lut = np.rint(np.clip(y, -20.0, 10.0) * 327.67).astype(np.int64)
     zeros = np.nonzero(lut == 0)[0] - 32768
     assert zeros.min() <= -650 and zeros.max() >= 650 and np.all(np.diff(zeros) == 1)
+
+
+# ---- the port against the reference on whole colour domains: where oracle/_ref is missing the port referees the
+# device's colour routes (tests/test_colour_routes_gpu.py), so it is held to the same rule there: bytes equal, but
+# that NaN on both sides counts as equal (tests/colour_domains.py)
+
+@needs_ref
+@pytest.mark.parametrize("space", ["scrgb", "xyz", "lab", "labs"])
+def test_port_vs_ref_on_every_colour(space):
+    from tests import colour_domains as dom
+
+    img = dom.cube()
+    want = Ref.run("colourspace", img, "space=" + space, cases.INTERP["srgb"])
+    dom.assert_same(PortCC.colourspace(img, space, "srgb"), want, "srgb -> " + space, img)
+
+
+def _port_wide_cases():
+    from tests import colour_domains as dom
+
+    return [(name, target) for name, target in dom.WIDE_CASES if (dom.WIDE[name][0], target) in PortCC._ROUTES]
+
+
+@needs_ref
+@pytest.mark.parametrize("name,target", _port_wide_cases(), ids=["%s-%s" % c for c in _port_wide_cases()])
+def test_port_vs_ref_on_wide_domains(name, target):
+    """The lattices of LabS, seeded Lab, the floats of every exponent and the special values for XYZ and scRGB: the
+    routes the port has, on the images the device kernels are given."""
+    from tests import colour_domains as dom
+
+    src, space = dom.wide_source(name)
+    want = Ref.run("colourspace", src, "space=" + target, cases.INTERP[space])
+    dom.assert_same(PortCC.colourspace(src, target, space), want, "%s -> %s" % (name, target), src)
