@@ -599,16 +599,43 @@ typedef struct _VipsThumbnailHip {
 	VipsSize size;
 	gboolean linear;
 	VipsInteresting crop;
+	gboolean no_rotate;
 } VipsThumbnailHip;
+
+/* A second object on @in's pixels that carries @image's orientation: the device image may be another operation's
+ * result (borrowed), so the tag never goes on @in itself. */
+static VipsHipImage *
+hip_oriented_view(VipsHipImage *in, VipsImage *image)
+{
+	VipsHipImage *view = NULL;
+
+	if (vips_hip_rot(in, &view, VIPS_ANGLE_D0))
+		return NULL;
+	if (vips_hip_image_set_orientation(view,
+			vips_image_get_typeof(image, VIPS_META_ORIENTATION) ? vips_image_get_orientation(image) : 0)) {
+		vips_hip_image_unref(view);
+		return NULL;
+	}
+
+	return view;
+}
 
 static int
 vips_thumbnail_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
 {
 	VipsThumbnailHip *thumbnail = (VipsThumbnailHip *) op;
 	int height = vips_object_argument_isset(VIPS_OBJECT(op), "height") ? thumbnail->height : 0;
+	VipsHipImage *view;
+	int result;
 
-	return vips_hip_thumbnail_image_crop(in, out, thumbnail->width, height, thumbnail->size,
-		thumbnail->linear, thumbnail->crop);
+	/* the orientation is the VipsImage's (thumbnail.c:592-599); the original rotates unless told not to */
+	if (!(view = hip_oriented_view(in, op->ready)))
+		return -1;
+	result = vips_hip_thumbnail_image_rotate(view, out, thumbnail->width, height, thumbnail->size,
+		thumbnail->linear, thumbnail->crop, thumbnail->no_rotate);
+	vips_hip_image_unref(view);
+
+	return result;
 }
 
 /* The plain case -- a 3-band uchar sRGB image, not linear, no crop: a resize by the factor
@@ -624,6 +651,9 @@ vips_thumbnail_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
 
 	if (thumbnail->linear || thumbnail->crop != VIPS_INTERESTING_NONE || in->Bands != 3 ||
 		in->BandFmt != VIPS_FORMAT_UCHAR || in->Type != VIPS_INTERPRETATION_sRGB)
+		return 1;
+	/* a rotation has no strip form (an output strip of a quarter turn is an input column band) */
+	if (!thumbnail->no_rotate && vips_image_get_orientation(in) != 1)
 		return 1;
 	hshrink = (double) in->Xsize / width;
 	vshrink = (double) in->Ysize / height;
@@ -646,9 +676,26 @@ vips_thumbnail_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
 HIP_SUBCLASS_FULL(VipsThumbnailHip, vips_thumbnail_hip, "thumbnail_image_hip",
 	"generate thumbnail from image (MI355X)", HIP_RESAMPLE_STRIPS(vips_thumbnail_hip))
 
+/* the rotated result has no orientation (vips_autorot removes it, autorot.c:185) */
+static int
+vips_thumbnail_hip_build(VipsObject *object)
+{
+	VipsHipOp *op = (VipsHipOp *) object;
+
+	if (VIPS_OBJECT_CLASS(vips_thumbnail_hip_parent_class)->build(object))
+		return -1;
+	if (!((VipsThumbnailHip *) object)->no_rotate)
+		vips_autorot_remove_angle(op->out);
+
+	return 0;
+}
+
 static void
 vips_thumbnail_hip_args(VipsThumbnailHipClass *class)
 {
+	VIPS_OBJECT_CLASS(class)->build = vips_thumbnail_hip_build;
+	VIPS_ARG_BOOL(class, "no_rotate", 115, "No rotate", "Don't use orientation tags to rotate image upright",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsThumbnailHip, no_rotate), FALSE);
 	VIPS_ARG_INT(class, "width", 3, "Target width", "Size to this width",
 		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsThumbnailHip, width), 1, VIPS_MAX_COORD, 1);
 	VIPS_ARG_INT(class, "height", 113, "Target height", "Size to this height",
@@ -686,6 +733,7 @@ typedef struct _VipsThumbnailFileHip {
 	VipsSize size;
 	gboolean linear;
 	VipsInteresting crop;
+	gboolean no_rotate;
 
 	VipsHipImage *result;
 	VipsPel *host;
@@ -744,8 +792,8 @@ vips_thumbnail_file_hip_build(VipsObject *object)
 	if (VIPS_OBJECT_CLASS(vips_thumbnail_file_hip_parent_class)->build(object))
 		return -1;
 
-	if (vips_hip_thumbnail(thumbnail->filename, &thumbnail->result, thumbnail->width, height,
-			thumbnail->size, thumbnail->linear, thumbnail->crop) ||
+	if (vips_hip_thumbnail_rotate(thumbnail->filename, &thumbnail->result, thumbnail->width, height,
+			thumbnail->size, thumbnail->linear, thumbnail->crop, thumbnail->no_rotate) ||
 		vips_hip_synchronize())
 		return hip_fail("thumbnail_hip");
 
@@ -755,6 +803,9 @@ vips_thumbnail_file_hip_build(VipsObject *object)
 		vips_hip_image_get_bands(thumbnail->result),
 		(VipsBandFormat) vips_hip_image_get_format(thumbnail->result), VIPS_CODING_NONE,
 		(VipsInterpretation) vips_hip_image_get_interpretation(thumbnail->result), 1.0, 1.0);
+	/* (with no_rotate the tag stays on the result, as on the original's) */
+	if (vips_hip_image_get_orientation(thumbnail->result))
+		vips_image_set_int(thumbnail->out, VIPS_META_ORIENTATION, vips_hip_image_get_orientation(thumbnail->result));
 	if (vips_image_pipelinev(thumbnail->out, VIPS_DEMAND_STYLE_ANY, NULL) ||
 		vips_image_generate(thumbnail->out,
 			vips_hip_op_start, vips_thumbnail_file_hip_gen, vips_hip_op_stop, NULL, thumbnail))
@@ -808,6 +859,8 @@ vips_thumbnail_file_hip_class_init(VipsThumbnailFileHipClass *class)
 		VIPS_TYPE_INTERESTING, VIPS_INTERESTING_NONE);
 	VIPS_ARG_BOOL(class, "linear", 118, "Linear", "Reduce in linear light",
 		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsThumbnailFileHip, linear), FALSE);
+	VIPS_ARG_BOOL(class, "no_rotate", 115, "No rotate", "Don't use orientation tags to rotate image upright",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsThumbnailFileHip, no_rotate), FALSE);
 }
 
 static void
@@ -1174,6 +1227,123 @@ static void
 vips_colourspace_hip_init(VipsColourspaceHip *c)
 {
 	c->space = VIPS_INTERPRETATION_sRGB;
+}
+
+/* rot_hip / flip_hip / autorot_hip: conversion/rot.c:402-440, flip.c:264-300, autorot.c:193-240.  They evaluate
+ * whole -- one device call, the result on the device for a downstream *_hip operation -- and have no strip form:
+ * an output strip of a quarter turn is an input column band.  An image over the HBM budget goes to the original
+ * operation (hip_wants_original). */
+typedef struct _VipsRotHip {
+	VipsHipOp parent_instance;
+	VipsAngle angle;
+} VipsRotHip;
+
+static int
+vips_rot_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_rot(in, out, ((VipsRotHip *) op)->angle);
+}
+
+HIP_SUBCLASS(VipsRotHip, vips_rot_hip, "rot_hip", "rotate an image (MI355X)")
+
+static void
+vips_rot_hip_args(VipsRotHipClass *class)
+{
+	VIPS_ARG_ENUM(class, "angle", 6, "Angle", "Angle to rotate image",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsRotHip, angle), VIPS_TYPE_ANGLE, VIPS_ANGLE_D90);
+}
+
+static void
+vips_rot_hip_init(VipsRotHip *rot)
+{
+	rot->angle = VIPS_ANGLE_D90;
+}
+
+typedef struct _VipsFlipHip {
+	VipsHipOp parent_instance;
+	VipsDirection direction;
+} VipsFlipHip;
+
+static int
+vips_flip_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_flip(in, out, ((VipsFlipHip *) op)->direction);
+}
+
+HIP_SUBCLASS(VipsFlipHip, vips_flip_hip, "flip_hip", "flip an image (MI355X)")
+
+static void
+vips_flip_hip_args(VipsFlipHipClass *class)
+{
+	VIPS_ARG_ENUM(class, "direction", 6, "Direction", "Direction to flip image",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsFlipHip, direction), VIPS_TYPE_DIRECTION,
+		VIPS_DIRECTION_HORIZONTAL);
+}
+
+static void
+vips_flip_hip_init(VipsFlipHip *flip)
+{
+	flip->direction = VIPS_DIRECTION_HORIZONTAL;
+}
+
+typedef struct _VipsAutorotHip {
+	VipsHipOp parent_instance;
+	VipsAngle angle;
+	gboolean flip;
+} VipsAutorotHip;
+
+static int
+vips_autorot_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsHipImage *view;
+	int result;
+
+	if (!(view = hip_oriented_view(in, op->ready)))
+		return -1;
+	result = vips_hip_autorot(view, out, NULL, NULL);
+	vips_hip_image_unref(view);
+
+	return result;
+}
+
+HIP_SUBCLASS(VipsAutorotHip, vips_autorot_hip, "autorot_hip", "autorotate image by exif tag (MI355X)")
+
+/* the two outputs are known at build time (autorot.c:119-165), and the result has no orientation (:185) */
+static int
+vips_autorot_hip_build(VipsObject *object)
+{
+	static const VipsAngle angles[9] = { VIPS_ANGLE_D0, VIPS_ANGLE_D0, VIPS_ANGLE_D0, VIPS_ANGLE_D180, VIPS_ANGLE_D180,
+		VIPS_ANGLE_D90, VIPS_ANGLE_D90, VIPS_ANGLE_D270, VIPS_ANGLE_D270 };
+	static const gboolean flips[9] = { FALSE, FALSE, TRUE, FALSE, TRUE, TRUE, FALSE, TRUE, FALSE };
+	VipsHipOp *op = (VipsHipOp *) object;
+	int orientation;
+
+	if (VIPS_OBJECT_CLASS(vips_autorot_hip_parent_class)->build(object))
+		return -1;
+	orientation = vips_image_get_orientation(op->in);
+	if (orientation < 1 || orientation > 8)
+		orientation = 1;
+	g_object_set(object, "angle", angles[orientation], "flip", flips[orientation], NULL);
+	vips_autorot_remove_angle(op->out);
+
+	return 0;
+}
+
+static void
+vips_autorot_hip_args(VipsAutorotHipClass *class)
+{
+	VIPS_OBJECT_CLASS(class)->build = vips_autorot_hip_build;
+	VIPS_ARG_ENUM(class, "angle", 6, "Angle", "Angle image was rotated by",
+		VIPS_ARGUMENT_OPTIONAL_OUTPUT, G_STRUCT_OFFSET(VipsAutorotHip, angle), VIPS_TYPE_ANGLE, VIPS_ANGLE_D0);
+	VIPS_ARG_BOOL(class, "flip", 7, "Flip", "Whether the image was flipped or not",
+		VIPS_ARGUMENT_OPTIONAL_OUTPUT, G_STRUCT_OFFSET(VipsAutorotHip, flip), FALSE);
+}
+
+static void
+vips_autorot_hip_init(VipsAutorotHip *autorot)
+{
+	autorot->angle = VIPS_ANGLE_D0;
+	autorot->flip = FALSE;
 }
 
 /* cast_hip: conversion/cast.c:470-520 */

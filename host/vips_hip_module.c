@@ -1546,7 +1546,8 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *   - premultiply / unpremultiply of double images (conversion/premultiply.c:155-230 makes double output);
  *   - thumbnail_image of images with fewer than 3 bands other than one-band uchar B_W, not linear -- grey +
  *     alpha, GREY16, linear one-band (resample/thumbnail.c:806-820) -- and with the content-driven crops
- *     (entropy, attention: conversion/smartcrop.c).
+ *     (entropy, attention: conversion/smartcrop.c);
+ *   - rot / flip / autorot of an image over the HBM budget (they have no strip form).
  */
 static gboolean
 hip_wants_original(VipsHipOp *op, VipsImage *in)
@@ -1557,6 +1558,11 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 		return TRUE;
 	if ((strcmp(nick, "premultiply_hip") == 0 || strcmp(nick, "unpremultiply_hip") == 0) &&
 		in->BandFmt == VIPS_FORMAT_DOUBLE)
+		return TRUE;
+	/* rot / flip / autorot have no strip form (an output strip of a quarter turn is an input column band): an
+	 * image that does not fit the HBM budget beside its result is the original's */
+	if ((strcmp(nick, "rot_hip") == 0 || strcmp(nick, "flip_hip") == 0 || strcmp(nick, "autorot_hip") == 0) &&
+		2 * (guint64) VIPS_IMAGE_SIZEOF_IMAGE(in) > hip_budget())
 		return TRUE;
 	if (strcmp(nick, "thumbnail_image_hip") == 0) {
 		gboolean linear = FALSE;
@@ -1691,7 +1697,7 @@ vips_hip_op_init(VipsHipOp *op)
 
 /* ------------------------------------------------------------------ subclasses */
 
-/* (the 17 operation classes: arguments, defaults, hooks) */
+/* (the 20 operation classes: arguments, defaults, hooks) */
 #include "vips_hip_classes.c"
 
 /* ------------------------------------------------------------------ registration */
@@ -1717,6 +1723,9 @@ g_module_check_init(GModule *module)
 	vips_sharpen_hip_get_type();
 	vips_colourspace_hip_get_type();
 	vips_cast_hip_get_type();
+	vips_rot_hip_get_type();
+	vips_flip_hip_get_type();
+	vips_autorot_hip_get_type();
 	vips_premultiply_hip_get_type();
 	vips_unpremultiply_hip_get_type();
 

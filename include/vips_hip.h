@@ -461,6 +461,18 @@ VIPS_HIP_API int vips_hip_cast_gen(const VipsHipRegion *in, const VipsHipRegion 
 VIPS_HIP_API int vips_hip_premultiply_gen(const VipsHipRegion *in, const VipsHipRegion *out,
 	double max_alpha, int uchar, int inverse);
 
+/* vips_rot (conversion/rot.c) and vips_flip (conversion/flip.c): exact copies of pels, any band count and
+ * format.  @angle is a VipsAngle (0 d0, 1 d90, 2 d180, 3 d270: d90 is a quarter turn clockwise, out(x, y) =
+ * in(y, H-1-x)), @direction a VipsDirection (0 horizontal, 1 vertical).  @in's width x height pels at its data go
+ * to @out's, which must have the turned size and the same bands and format; strides are free (a window of a larger
+ * image on either side), left / top are not looked at.  Quarter turns run in a transposing tile kernel for pels of
+ * 1, 2, 3, 4, 6, 8, 12 and 16 bytes (vips_hip_rot_tile_side: its tile side for a pel size, 0 for others), the
+ * other operations in a streaming kernel where rows start on dwords; a one-pel-a-lane kernel takes the rest.
+ */
+VIPS_HIP_API int vips_hip_rot_gen(int angle, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_flip_gen(int direction, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_rot_tile_side(int pel_size);
+
 /* vips_sharpen_generate (convolution/sharpen.c:116-168): LabS in, LabS out; the
  * blurred L band comes from a vips_hip_conv_gen pass the caller ran.
  */
@@ -496,9 +508,20 @@ VIPS_HIP_API int vips_hip_image_get_format(const VipsHipImage *image);
 VIPS_HIP_API int vips_hip_image_get_interpretation(const VipsHipImage *image);
 VIPS_HIP_API size_t vips_hip_image_get_stride(const VipsHipImage *image);
 VIPS_HIP_API void vips_hip_image_region(const VipsHipImage *image, VipsHipRegion *region);
+/* The EXIF-style orientation, the one piece of metadata an image carries: 1 .. 8, or 0 for an image that has none
+ * (read as 1, as vips_image_get_orientation does).  Images made by the constructors above have none; the JPEG
+ * loader sets it from the EXIF tag and the .v loader from the file's metadata.  vips_hip_rot and vips_hip_flip
+ * carry it through unchanged (as the reference does), vips_hip_autorot acts on it and clears it, the
+ * vips_hip_thumbnail*_rotate entry points act on it or keep it; EVERY OTHER operation's result has none.
+ */
+VIPS_HIP_API int vips_hip_image_get_orientation(const VipsHipImage *image);
+VIPS_HIP_API int vips_hip_image_set_orientation(VipsHipImage *image, int orientation);
 
 /* The native ".v" format (doc/file-format.md; iofuncs/vips.c:283-441): 64-byte header, then
- * band-interleaved scanlines without padding, then optional XML metadata (not carried here).
+ * band-interleaved scanlines without padding, then optional XML metadata (iofuncs/vips.c:560-622), of which the
+ * orientation is carried and nothing else: the loader reads <field type="gint" name="orientation"> inside <meta>, the
+ * saver appends a trailer with that one field to an image that has an orientation, and to no other (such a file is
+ * header + pixels).  vips_hip_vfile_read_orientation is host-only: 0 for a file without one.
  * vips_hip_vfile_read_header is host-only (vips__read_header_bytes plus the file-length check of
  * iofuncs/image.c:966-979); the loader and the saver move the pixels between the file and HBM
  * through two pinned buffers so that disc and PCIe transfers overlap (the role of the two
@@ -518,6 +541,7 @@ typedef struct _VipsHipVHeader {
 } VipsHipVHeader;
 
 VIPS_HIP_API int vips_hip_vfile_read_header(const char *path, VipsHipVHeader *header);
+VIPS_HIP_API int vips_hip_vfile_read_orientation(const char *path, int *orientation);
 VIPS_HIP_API VipsHipImage *vips_hip_image_new_from_vfile(const char *path);
 VIPS_HIP_API int vips_hip_image_write_to_vfile(const VipsHipImage *image, const char *path);
 
@@ -527,8 +551,14 @@ VIPS_HIP_API int vips_hip_image_write_to_vfile(const VipsHipImage *image, const 
  * at first use.  vips_hip_thumbnail is vips_thumbnail() (resample/thumbnail.c:549-676 open +
  * :678-1067 build) for JPEG and .v files: vips_thumbnail_find_jpegshrink (:488-519) picks the
  * block shrink, the pre-shrunk image is uploaded, the rest is vips_hip_thumbnail_image.  Files
- * that need auto-rotation, or ICC colour management (an embedded profile in linear mode), are
- * refused.
+ * that need ICC colour management (an embedded profile in linear mode) are refused.
+ *
+ * Auto-rotation: the *_rotate entry points are vips_thumbnail with its no_rotate argument.  With @no_rotate 0
+ * an orientation that swaps the axes (5 .. 8) swaps the target box for the shrink calculation (thumbnail.c:416-420,
+ * vips_hip_thumbnail_find_jpegshrink_rotate's @swap), vips_autorot runs after the conversion back to the output
+ * space and before the crop (:989-1062), and the result has no orientation; with @no_rotate 1 the pixels stay as
+ * stored and the result keeps the tag.  The entry points without the argument are as they were before there was
+ * auto-rotation: vips_hip_thumbnail refuses a JPEG whose orientation is not 1 and ignores a .v file's.
  */
 typedef struct _VipsHipJpegHeader {
 	int width, height;             /* after the shrink */
@@ -541,11 +571,15 @@ typedef struct _VipsHipJpegHeader {
 
 VIPS_HIP_API int vips_hip_thumbnail_find_jpegshrink(int in_width, int in_height,
 	int width, int height, int size, int linear, int crop);
+VIPS_HIP_API int vips_hip_thumbnail_find_jpegshrink_rotate(int in_width, int in_height,
+	int width, int height, int size, int linear, int crop, int swap);
 VIPS_HIP_API int vips_hip_jpeg_read_header(const char *path, int shrink, VipsHipJpegHeader *header);
 VIPS_HIP_API int vips_hip_jpeg_read_to_memory(const char *path, int shrink, void *host_data, size_t size);
 VIPS_HIP_API VipsHipImage *vips_hip_image_new_from_jpeg(const char *path, int shrink);
 VIPS_HIP_API int vips_hip_thumbnail(const char *path, VipsHipImage **out,
 	int width, int height, int size, int linear, int crop);
+VIPS_HIP_API int vips_hip_thumbnail_rotate(const char *path, VipsHipImage **out,
+	int width, int height, int size, int linear, int crop, int no_rotate);
 /* @n files on @n_threads host threads, each with its own stream: decode, upload and device work
  * of different files overlap (the shape of BASELINE config C4 when the inputs are files).
  * Returns the number of failures; outs[i] is NULL for those and, when @errors is given
@@ -553,6 +587,8 @@ VIPS_HIP_API int vips_hip_thumbnail(const char *path, VipsHipImage **out,
  */
 VIPS_HIP_API int vips_hip_thumbnail_batch(const char *const *paths, int n, VipsHipImage **outs,
 	char *errors, int width, int height, int size, int linear, int crop, int n_threads);
+VIPS_HIP_API int vips_hip_thumbnail_batch_rotate(const char *const *paths, int n, VipsHipImage **outs,
+	char *errors, int width, int height, int size, int linear, int crop, int no_rotate, int n_threads);
 
 /* Emulate the reference sink's strip height when seeding the reduce position
  * accumulators (see vips_hip_reducev_gen_tiled); default 16 = vips__fatstrip_height
@@ -583,8 +619,8 @@ VIPS_HIP_API int vips_hip_resize(VipsHipImage *in, VipsHipImage **out,
  * :413-467): processing-space conversion, the shrink for the target box and fit mode,
  * vips_resize, conversion back.  @height <= 0 means == @width; @size is a VipsSize
  * (include/vips/resample.h: 0 both, 1 up, 2 down, 3 force); @linear shrinks in scRGB.
- * Images with alpha are premultiplied around the resize (thumbnail.c:848-904).  Crop,
- * auto-rotate and ICC are outside the path: images that need them are refused.
+ * Images with alpha are premultiplied around the resize (thumbnail.c:848-904).  This entry point does not look
+ * at the image's orientation (vips_hip_thumbnail_image_rotate does); ICC is outside the path.
  */
 VIPS_HIP_API int vips_hip_thumbnail_image(VipsHipImage *in, VipsHipImage **out,
 	int width, int height, int size, int linear);
@@ -595,6 +631,15 @@ VIPS_HIP_API int vips_hip_thumbnail_image(VipsHipImage *in, VipsHipImage **out,
  */
 VIPS_HIP_API int vips_hip_thumbnail_image_crop(VipsHipImage *in, VipsHipImage **out,
 	int width, int height, int size, int linear, int crop);
+/* ... with vips_thumbnail's auto-rotation by the image's orientation (see vips_hip_thumbnail_rotate above). */
+VIPS_HIP_API int vips_hip_thumbnail_image_rotate(VipsHipImage *in, VipsHipImage **out,
+	int width, int height, int size, int linear, int crop, int no_rotate);
+/* vips_rot / vips_flip (@angle, @direction as in vips_hip_rot_gen; d0 shares the pixels) and vips_autorot
+ * (conversion/autorot.c:103-191): the turn and flip that undo the image's orientation, as ONE launch; the result
+ * has no orientation; @angle (a VipsAngle) and @flip say what was done and may be NULL. */
+VIPS_HIP_API int vips_hip_rot(VipsHipImage *in, VipsHipImage **out, int angle);
+VIPS_HIP_API int vips_hip_flip(VipsHipImage *in, VipsHipImage **out, int direction);
+VIPS_HIP_API int vips_hip_autorot(VipsHipImage *in, VipsHipImage **out, int *angle, int *flip);
 /* vips_extract_area (conversion/extract.c:137-187). */
 VIPS_HIP_API int vips_hip_extract_area(VipsHipImage *in, VipsHipImage **out,
 	int left, int top, int width, int height);

@@ -240,6 +240,21 @@ _SIGNATURES = {
                                              c_double, c_double, c_double, c_double, c_double, c_double, c_int]),
     "vips_hip_gaussblur_colourspace": (c_int, [c_void_p, P(c_void_p), c_double, c_double, c_int, c_int]),
     "vips_hip_cast": (c_int, [c_void_p, P(c_void_p), c_int]),
+    # rot / flip / autorot, the orientation
+    "vips_hip_rot_gen": (c_int, [c_int, RegionP, RegionP]),
+    "vips_hip_flip_gen": (c_int, [c_int, RegionP, RegionP]),
+    "vips_hip_rot_tile_side": (c_int, [c_int]),
+    "vips_hip_rot": (c_int, [c_void_p, P(c_void_p), c_int]),
+    "vips_hip_flip": (c_int, [c_void_p, P(c_void_p), c_int]),
+    "vips_hip_autorot": (c_int, [c_void_p, P(c_void_p), P(c_int), P(c_int)]),
+    "vips_hip_image_get_orientation": (c_int, [c_void_p]),
+    "vips_hip_image_set_orientation": (c_int, [c_void_p, c_int]),
+    "vips_hip_vfile_read_orientation": (c_int, [c_char_p, P(c_int)]),
+    "vips_hip_thumbnail_find_jpegshrink_rotate": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vips_hip_thumbnail_image_rotate": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vips_hip_thumbnail_rotate": (c_int, [c_char_p, P(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
+    "vips_hip_thumbnail_batch_rotate": (c_int, [P(c_char_p), c_int, P(c_void_p), c_char_p, c_int, c_int, c_int,
+                                                c_int, c_int, c_int, c_int]),
     "vips_hip_premultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_unpremultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
 }

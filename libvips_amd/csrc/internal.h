@@ -137,12 +137,22 @@ struct _VipsHipImage {
 	// library memory is shared between image objects (vips_copy-style no-op results): the
 	// last holder returns it to the pool
 	std::shared_ptr<void> hold;
+	// EXIF-style orientation, 1 .. 8; 0: the image has none (read as 1, vips_image_get_orientation, iofuncs/header.c).
+	// Set by the JPEG and .v loaders and vips_hip_image_set_orientation, carried by vips_hip_rot / vips_hip_flip,
+	// cleared by vips_hip_autorot; every other operation's result has none.
+	int orientation = 0;
 };
 
 namespace vh {
 // Run where the data lives: make sure a device is selected and bind the calling thread to the
 // device `image` is on (every image-level operation starts with this).
 int bind_to(const _VipsHipImage *image);
-// A second image object on the same pixels (library-owned images only; nullptr otherwise).
+// A second image object on the same pixels (library-owned images only; nullptr otherwise).  It has no orientation.
 _VipsHipImage *image_share(const _VipsHipImage *in);
+// rot.hip: out = in turned and / or mirrored in one launch; op is a sum of ROT_OP_*
+enum { ROT_OP_TRANSPOSE = 1, ROT_OP_FLIPX = 2, ROT_OP_FLIPY = 4 };
+int rot_op_gen(const char *domain, int op, const VipsHipRegion *in, const VipsHipRegion *out);
+// the operation vips_autorot runs for an orientation (autorot.c:119-160 folded: a turn and the flip behind it are
+// one operation here); 0 for orientations that change nothing
+int orientation_op(int orientation);
 } // namespace vh

@@ -14,9 +14,10 @@
 // The entropy decode is libjpeg's and runs on the host (the same IJG library the reference
 // build links, loaded with dlopen so that libvipship.so itself does not depend on it); the
 // pre-shrunk image -- 1/4 to 1/64 of the pixels -- is uploaded and everything after it runs on
-// the device.  Auto-rotation (EXIF orientation other than 1) and ICC colour management (an
-// embedded profile in linear mode) are outside the path: such files are refused rather than
-// thumbnailed wrongly.
+// the device, auto-rotation by the EXIF orientation included (vips_hip_thumbnail_rotate: rot.hip, one
+// short launch on the thumbnail; vips_hip_thumbnail, the entry point without it, refuses an oriented
+// file).  ICC colour management (an embedded profile in linear mode) is outside the path: such files
+// are refused rather than thumbnailed wrongly.
 #include "internal.h"
 
 #include <csetjmp>
@@ -292,6 +293,14 @@ extern "C" {
 int vips_hip_thumbnail_find_jpegshrink(int in_width, int in_height, int width, int height, int size,
 	int linear, int crop)
 {
+	return vips_hip_thumbnail_find_jpegshrink_rotate(in_width, in_height, width, height, size, linear, crop, 0);
+}
+
+// ... for an image that will be turned by a quarter afterwards (@swap): the target box is swapped for the shrink
+// calculation (thumbnail.c:416-420)
+int vips_hip_thumbnail_find_jpegshrink_rotate(int in_width, int in_height, int width, int height, int size,
+	int linear, int crop, int swap)
+{
 	if (in_width <= 0 || in_height <= 0 || width <= 0) {
 		error("thumbnail", "bad dimensions");
 		return -1;
@@ -299,7 +308,7 @@ int vips_hip_thumbnail_find_jpegshrink(int in_width, int in_height, int width, i
 	if (height <= 0)
 		height = width;
 	double hshrink, vshrink;
-	calculate_shrink(in_width, in_height, width, height, size, crop, &hshrink, &vshrink);
+	calculate_shrink(in_width, in_height, swap ? height : width, swap ? width : height, size, crop, &hshrink, &vshrink);
 	const double shrink = hshrink < vshrink ? hshrink : vshrink;
 	// libjpeg shrinks in Y of YCbCr, not in linear light (thumbnail.c:497-501)
 	if (linear)
@@ -350,14 +359,20 @@ VipsHipImage *vips_hip_image_new_from_jpeg(const char *path, int shrink)
 	std::vector<unsigned char> pixels((size_t) h.width * h.height * h.bands);
 	if (vips_hip_jpeg_read_to_memory(path, shrink, pixels.data(), pixels.size()))
 		return nullptr;
-	return vips_hip_image_new_from_memory(pixels.data(), h.width, h.height, h.bands, VIPS_HIP_FORMAT_UCHAR,
+	VipsHipImage *im = vips_hip_image_new_from_memory(pixels.data(), h.width, h.height, h.bands, VIPS_HIP_FORMAT_UCHAR,
 		h.interpretation);
+	if (im && h.orientation >= 1 && h.orientation <= 8)
+		im->orientation = h.orientation;
+	return im;
 }
 
 // vips_thumbnail (thumbnail.c:1130-1330 file class + :549-676 open + :678-1067 build) for
 // JPEG and .v files.
-int vips_hip_thumbnail(const char *path, VipsHipImage **out, int width, int height, int size, int linear,
-	int crop)
+//
+// @rotate: -1 the entry point without auto-rotation (an oriented JPEG is refused, a .v file's orientation ignored),
+// 0 vips_thumbnail's default (the orientation is undone), 1 its no_rotate (pixels as stored, the tag stays)
+static int thumbnail_file(const char *path, VipsHipImage **out, int width, int height, int size, int linear, int crop,
+	int rotate)
 {
 	if (!path || !out) {
 		error("thumbnail", "null argument");
@@ -372,7 +387,7 @@ int vips_hip_thumbnail(const char *path, VipsHipImage **out, int width, int heig
 		VipsHipJpegHeader h;
 		if (vips_hip_jpeg_read_header(path, 1, &h))
 			return -1;
-		if (h.orientation > 1) {
+		if (rotate < 0 && h.orientation > 1) {
 			error("thumbnail", "\"%s\" needs auto-rotation (EXIF orientation %d): outside the HIP path", path,
 				h.orientation);
 			return -1;
@@ -389,7 +404,8 @@ int vips_hip_thumbnail(const char *path, VipsHipImage **out, int width, int heig
 			error("thumbnail", "\"%s\": CMYK JPEGs need an ICC import: outside the HIP path", path);
 			return -1;
 		}
-		const int factor = vips_hip_thumbnail_find_jpegshrink(h.width, h.height, width, height, size, linear, crop);
+		const int factor = vips_hip_thumbnail_find_jpegshrink_rotate(h.width, h.height, width, height, size, linear, crop,
+			rotate == 0 && h.orientation >= 5 && h.orientation <= 8);
 		if (factor < 0)
 			return -1;
 		loaded = vips_hip_image_new_from_jpeg(path, factor);
@@ -398,9 +414,22 @@ int vips_hip_thumbnail(const char *path, VipsHipImage **out, int width, int heig
 		loaded = vips_hip_image_new_from_vfile(path);
 	if (!loaded)
 		return -1;
-	const int r = vips_hip_thumbnail_image_crop(loaded, out, width, height, size, linear, crop);
+	const int r = rotate < 0 ? vips_hip_thumbnail_image_crop(loaded, out, width, height, size, linear, crop)
+							 : vips_hip_thumbnail_image_rotate(loaded, out, width, height, size, linear, crop, rotate);
 	vips_hip_image_unref(loaded);
 	return r;
+}
+
+int vips_hip_thumbnail(const char *path, VipsHipImage **out, int width, int height, int size, int linear,
+	int crop)
+{
+	return thumbnail_file(path, out, width, height, size, linear, crop, -1);
+}
+
+int vips_hip_thumbnail_rotate(const char *path, VipsHipImage **out, int width, int height, int size, int linear,
+	int crop, int no_rotate)
+{
+	return thumbnail_file(path, out, width, height, size, linear, crop, no_rotate ? 1 : 0);
 }
 
 // A batch of files on `n_threads` host threads: every thread decodes, uploads and thumbnails on
@@ -409,8 +438,8 @@ int vips_hip_thumbnail(const char *path, VipsHipImage **out, int width, int heig
 // from a caller running vips_thumbnail() on several threads; BASELINE config C4 is this shape.
 // Returns the number of files that failed; outs[i] is NULL and errors[i] (if given, 256 bytes
 // each) holds the message for those.
-int vips_hip_thumbnail_batch(const char *const *paths, int n, VipsHipImage **outs, char *errors, int width,
-	int height, int size, int linear, int crop, int n_threads)
+static int thumbnail_batch_any(const char *const *paths, int n, VipsHipImage **outs, char *errors, int width,
+	int height, int size, int linear, int crop, int rotate, int n_threads)
 {
 	if (!paths || !outs || n < 0) {
 		error("thumbnail", "null argument");
@@ -427,7 +456,7 @@ int vips_hip_thumbnail_batch(const char *const *paths, int n, VipsHipImage **out
 			if (i >= n)
 				break;
 			outs[i] = nullptr;
-			if (vips_hip_thumbnail(paths[i], &outs[i], width, height, size, linear, crop)) {
+			if (thumbnail_file(paths[i], &outs[i], width, height, size, linear, crop, rotate)) {
 				outs[i] = nullptr;
 				failed.fetch_add(1);
 				if (errors) {
@@ -457,6 +486,18 @@ int vips_hip_thumbnail_batch(const char *const *paths, int n, VipsHipImage **out
 			t.join();
 	}
 	return failed.load();
+}
+
+int vips_hip_thumbnail_batch(const char *const *paths, int n, VipsHipImage **outs, char *errors, int width,
+	int height, int size, int linear, int crop, int n_threads)
+{
+	return thumbnail_batch_any(paths, n, outs, errors, width, height, size, linear, crop, -1, n_threads);
+}
+
+int vips_hip_thumbnail_batch_rotate(const char *const *paths, int n, VipsHipImage **outs, char *errors, int width,
+	int height, int size, int linear, int crop, int no_rotate, int n_threads)
+{
+	return thumbnail_batch_any(paths, n, outs, errors, width, height, size, linear, crop, no_rotate ? 1 : 0, n_threads);
 }
 
 } // extern "C"

@@ -1505,8 +1505,12 @@ int vips_hip_thumbnail_image(VipsHipImage *in, VipsHipImage **out, int width, in
 // ... with the crop argument: a VipsInteresting (include/vips/conversion.h:97-107).  The
 // positional modes are here (none 0, centre 1, low 4, high 5, all 6: smartcrop.c:359-400); the
 // content-driven ones (entropy 2, attention 3) are outside the path.
-int vips_hip_thumbnail_image_crop(VipsHipImage *in, VipsHipImage **out, int width, int height, int size,
-	int linear, int crop)
+//
+// @rotate: the orientation vips_autorot undoes between the conversion back to the output space and the crop
+// (thumbnail.c:989-1062), 0 or 1 for none.  One that swaps the axes (5 .. 8) swaps the target box for the shrink
+// calculation (thumbnail.c:416-420), so that the crop works on the upright image with the box as given.
+static int thumbnail_image_any(VipsHipImage *in, VipsHipImage **out, int width, int height, int size, int linear,
+	int crop, int rotate)
 {
 	if (in && vh::bind_to(in)) // run where the pixels live
 		return -1;
@@ -1560,9 +1564,10 @@ int vips_hip_thumbnail_image_crop(VipsHipImage *in, VipsHipImage **out, int widt
 		}
 	}
 
-	// vips_thumbnail_calculate_shrink, thumbnail.c:413-467 (crop NONE, no rotate)
-	double hshrink = (double) cur->width / width;
-	double vshrink = (double) cur->height / height;
+	// vips_thumbnail_calculate_shrink, thumbnail.c:413-467
+	const bool swap = rotate >= 5 && rotate <= 8;
+	double hshrink = (double) cur->width / (swap ? height : width);
+	double vshrink = (double) cur->height / (swap ? width : height);
 	// fit the box (the bigger shrink wins) or, when cropping, fill it (the smaller one)
 	const bool horizontal = crop != 0 ? (hshrink < vshrink) : !(hshrink < vshrink);
 	if (size != 3) { // != VIPS_SIZE_FORCE
@@ -1631,6 +1636,14 @@ int vips_hip_thumbnail_image_crop(VipsHipImage *in, VipsHipImage **out, int widt
 		vips_hip_image_unref(resized.im);
 		resized.im = back.release();
 	}
+	if (vh::orientation_op(rotate) != 0) { // thumbnail.c:989-997
+		resized.im->orientation = rotate;
+		ImageRef upright;
+		if (vips_hip_autorot(resized.im, &upright.im, nullptr, nullptr))
+			return -1;
+		vips_hip_image_unref(resized.im);
+		resized.im = upright.release();
+	}
 	if (crop != 0) { // thumbnail.c:1010-1038 -> vips_smartcrop's positional modes
 		const VipsHipImage *r = resized.im;
 		int crop_width = width < r->width ? width : r->width;
@@ -1651,6 +1664,123 @@ int vips_hip_thumbnail_image_crop(VipsHipImage *in, VipsHipImage **out, int widt
 		return vips_hip_extract_area(resized.im, out, left, top, crop_width, crop_height);
 	}
 	*out = resized.release();
+	return 0;
+}
+
+int vips_hip_thumbnail_image_crop(VipsHipImage *in, VipsHipImage **out, int width, int height, int size,
+	int linear, int crop)
+{
+	return thumbnail_image_any(in, out, width, height, size, linear, crop, 0);
+}
+
+// ... with vips_thumbnail's auto-rotation: the image's orientation is undone (@no_rotate 0; the result has none), or
+// the pixels are left as stored and the result keeps it (@no_rotate 1)
+int vips_hip_thumbnail_image_rotate(VipsHipImage *in, VipsHipImage **out, int width, int height, int size,
+	int linear, int crop, int no_rotate)
+{
+	if (!in || !out) {
+		error("thumbnail", "null argument");
+		return -1;
+	}
+	const int orientation = in->orientation;
+	if (thumbnail_image_any(in, out, width, height, size, linear, crop, no_rotate ? 0 : orientation))
+		return -1;
+	if (no_rotate)
+		(*out)->orientation = orientation; // (the result is an object of its own even where it shares pixels)
+	return 0;
+}
+
+// vips_rot, conversion/rot.c:349-400; vips_flip, conversion/flip.c:230-262; vips_autorot, conversion/autorot.c:103-191
+static int rot_image(const char *domain, VipsHipImage *in, VipsHipImage **out, int op, int orientation)
+{
+	if (in && vh::bind_to(in)) // run where the pixels live
+		return -1;
+	if (!in || !out) {
+		error(domain, "null argument");
+		return -1;
+	}
+	if (op == 0) { // vips_copy: the same pixels
+		VipsHipImage *shared = image_share(in);
+		if (!shared) {
+			ImageRef c(vips_hip_image_new(in->width, in->height, in->bands, in->format, in->interpretation));
+			if (!c.im || vips_hip_memcpy_d2d(c.im->data, in->data, in->stride * in->height))
+				return -1;
+			shared = c.release();
+		}
+		shared->orientation = orientation;
+		*out = shared;
+		return 0;
+	}
+	const bool transpose = (op & vh::ROT_OP_TRANSPOSE) != 0;
+	ImageRef o(vips_hip_image_new(transpose ? in->height : in->width, transpose ? in->width : in->height, in->bands,
+		in->format, in->interpretation));
+	if (!o.im)
+		return -1;
+	VipsHipRegion ri, ro;
+	vips_hip_image_region(in, &ri);
+	vips_hip_image_region(o.im, &ro);
+	if (vh::rot_op_gen(domain, op, &ri, &ro))
+		return -1;
+	o.im->orientation = orientation;
+	*out = o.release();
+	return 0;
+}
+
+int vips_hip_rot(VipsHipImage *in, VipsHipImage **out, int angle)
+{
+	static const int ops[4] = { 0, vh::ROT_OP_TRANSPOSE | vh::ROT_OP_FLIPY, vh::ROT_OP_FLIPX | vh::ROT_OP_FLIPY,
+		vh::ROT_OP_TRANSPOSE | vh::ROT_OP_FLIPX };
+	if (angle < 0 || angle > 3) {
+		error("rot", "bad angle %d", angle);
+		return -1;
+	}
+	return rot_image("rot", in, out, ops[angle], in ? in->orientation : 0);
+}
+
+int vips_hip_flip(VipsHipImage *in, VipsHipImage **out, int direction)
+{
+	if (direction != 0 && direction != 1) {
+		error("flip", "bad direction %d", direction);
+		return -1;
+	}
+	return rot_image("flip", in, out, direction == 0 ? vh::ROT_OP_FLIPX : vh::ROT_OP_FLIPY, in ? in->orientation : 0);
+}
+
+int vips_hip_autorot(VipsHipImage *in, VipsHipImage **out, int *angle, int *flip)
+{
+	if (!in || !out) {
+		error("autorot", "null argument");
+		return -1;
+	}
+	// autorot.c:119-160
+	static const int angles[9] = { 0, 0, 0, 2, 2, 1, 1, 3, 3 };
+	static const int flips[9] = { 0, 0, 1, 0, 1, 1, 0, 1, 0 };
+	const int orientation = in->orientation >= 1 && in->orientation <= 8 ? in->orientation : 1;
+	if (rot_image("autorot", in, out, vh::orientation_op(orientation), 0))
+		return -1;
+	if (angle)
+		*angle = angles[orientation];
+	if (flip)
+		*flip = flips[orientation];
+	return 0;
+}
+
+int vips_hip_image_get_orientation(const VipsHipImage *image)
+{
+	return image && image->orientation >= 1 && image->orientation <= 8 ? image->orientation : 0;
+}
+
+int vips_hip_image_set_orientation(VipsHipImage *image, int orientation)
+{
+	if (!image) {
+		error("VipsImage", "null argument");
+		return -1;
+	}
+	if (orientation < 0 || orientation > 8) {
+		error("VipsImage", "orientation %d is not 0 (none) or 1 .. 8", orientation);
+		return -1;
+	}
+	image->orientation = orientation;
 	return 0;
 }
 

@@ -205,7 +205,9 @@ _VipsHipImage *image_share(const _VipsHipImage *in)
 {
 	if (!in || !in->owns || !in->hold)
 		return nullptr;
-	return new _VipsHipImage(*in);
+	_VipsHipImage *shared = new _VipsHipImage(*in);
+	shared->orientation = 0;
+	return shared;
 }
 
 int check_region(const char *domain, const VipsHipRegion *r)

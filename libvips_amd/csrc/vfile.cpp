@@ -8,8 +8,8 @@
 // Type (int32), Xres, Yres (float32), Length (int32), Compression, Level (int16), Xoffset,
 // Yoffset (int32) in the byte order the magic names, zero padding -- followed by the pixels as
 // band-interleaved scanlines without padding, followed by an optional XML block of metadata.
-// A file shorter than header + pixels is refused (iofuncs/image.c:966-979); anything behind the
-// pixels is metadata this path does not carry.
+// A file shorter than header + pixels is refused (iofuncs/image.c:966-979); of the metadata behind
+// the pixels this path carries the orientation and nothing else.
 //
 // What a sink does with two buffers on the CPU (sinkdisc.c:195-220: one buffer is written in
 // the background while workers fill the other) is done here with two pinned host buffers: the
@@ -20,6 +20,7 @@
 #include <cerrno>
 #include <cstdio>
 #include <cstring>
+#include <string>
 
 #include <sys/stat.h>
 
@@ -160,9 +161,70 @@ struct Staging {
 	}
 };
 
+// The XML trailer behind the pixels (vips__write_extension_block / vips__read_extension_block,
+// iofuncs/vips.c:560-622, 762-880) carries an image's metadata.  Of it only the orientation is read, by a scan for
+// <field type="gint" name="orientation">N</field> inside a complete <meta> element; nothing else is carried.
+// Returns 0 when there is no trailer, no such field, or the trailer is cut short.
+const size_t TRAILER_MOST = 64u << 20;
+
+int scan_orientation(const std::string &xml)
+{
+	const size_t meta = xml.find("<meta>");
+	if (meta == std::string::npos)
+		return 0;
+	const size_t end = xml.find("</meta>", meta);
+	if (end == std::string::npos)
+		return 0;
+	static const char tag[] = "<field type=\"gint\" name=\"orientation\">";
+	size_t at = xml.find(tag, meta);
+	if (at == std::string::npos || at > end)
+		return 0;
+	at += sizeof(tag) - 1;
+	int value = 0, digits = 0;
+	while (at < end && xml[at] >= '0' && xml[at] <= '9' && digits < 4) {
+		value = value * 10 + (xml[at] - '0');
+		at++;
+		digits++;
+	}
+	if (!digits || xml.compare(at, 8, "</field>") != 0)
+		return 0;
+	return value >= 1 && value <= 8 ? value : 0;
+}
+
+int read_orientation(FILE *f, const VipsHipVHeader &h)
+{
+	if (fseek(f, 0, SEEK_END))
+		return 0;
+	const long long size = ftell(f);
+	const long long from = h.data_offset + h.data_size;
+	if (size <= from || fseek(f, (long) from, SEEK_SET))
+		return 0;
+	std::string xml((size_t) (size - from) < TRAILER_MOST ? (size_t) (size - from) : TRAILER_MOST, '\0');
+	xml.resize(fread(&xml[0], 1, xml.size(), f));
+	return scan_orientation(xml);
+}
+
 } // namespace
 
 extern "C" {
+
+int vips_hip_vfile_read_orientation(const char *path, int *orientation)
+{
+	if (!path || !orientation) {
+		error("VipsImage", "null argument");
+		return -1;
+	}
+	VipsHipVHeader h;
+	if (vips_hip_vfile_read_header(path, &h))
+		return -1;
+	File file(fopen(path, "rb"));
+	if (!file.f) {
+		error("VipsImage", "unable to open \"%s\": %s", path, strerror(errno));
+		return -1;
+	}
+	*orientation = read_orientation(file.f, h);
+	return 0;
+}
 
 int vips_hip_vfile_read_header(const char *path, VipsHipVHeader *header)
 {
@@ -249,6 +311,7 @@ VipsHipImage *vips_hip_image_new_from_vfile(const char *path)
 		vips_hip_image_unref(im);
 		return nullptr;
 	}
+	im->orientation = read_orientation(file.f, h);
 	return im;
 }
 
@@ -332,6 +395,15 @@ int vips_hip_image_write_to_vfile(const VipsHipImage *image, const char *path)
 		}
 		at = next_at;
 		n = next_n;
+	}
+	// the metadata trailer, only for an image that has an orientation (every other file stays header + pixels)
+	if (image->orientation >= 1 && image->orientation <= 8 &&
+		fprintf(file.f,
+			"<?xml version=\"1.0\"?>\n<root xmlns=\"http://www.vips.ecs.soton.ac.uk/vips/8.19.0\">\n  <header>\n"
+			"  </header>\n  <meta>\n    <field type=\"gint\" name=\"orientation\">%d</field>\n  </meta>\n</root>\n",
+			image->orientation) < 0) {
+		error("VipsImage", "write failed for \"%s\"", path);
+		return -1;
 	}
 	if (fflush(file.f)) {
 		error("VipsImage", "write failed for \"%s\"", path);

@@ -59,6 +59,10 @@ PRECISIONS = {"integer": 0, "float": 1, "approximate": 2}
 # VipsSize (include/vips/resample.h), VipsInteresting (include/vips/conversion.h:97-107)
 SIZES = {"both": 0, "up": 1, "down": 2, "force": 3}
 INTERESTING = {"none": 0, "centre": 1, "entropy": 2, "attention": 3, "low": 4, "high": 5, "all": 6}
+# VipsAngle, VipsDirection (include/vips/conversion.h)
+ANGLES = {"d0": 0, "d90": 1, "d180": 2, "d270": 3}
+ANGLE_NAMES = {v: k for k, v in ANGLES.items()}
+DIRECTIONS = {"horizontal": 0, "vertical": 1}
 # VipsInterpretation (include/vips/image.h:94-118)
 INTERPRETATIONS = {
     "multiband": 0,
@@ -180,6 +184,20 @@ class Image(object):
         return INTERPRETATION_NAMES.get(v, v)
 
     @property
+    def orientation(self):
+        """The EXIF-style orientation, 1 .. 8 (an image without one reads as 1, as in pyvips); ``has_orientation``
+        tells the two apart.  Set by the JPEG and .v loaders, kept by rot / flip, undone by autorot."""
+        return lib.vips_hip_image_get_orientation(self._h) or 1
+
+    @orientation.setter
+    def orientation(self, value):
+        check(lib.vips_hip_image_set_orientation(self._h, int(value) if value else 0))
+
+    @property
+    def has_orientation(self):
+        return lib.vips_hip_image_get_orientation(self._h) != 0
+
+    @property
     def data_ptr(self):
         return lib.vips_hip_image_get_data(self._h)
 
@@ -236,15 +254,23 @@ class Image(object):
         return cls(check_handle(lib.vips_hip_image_new_from_jpeg(os.fsencode(path), int(shrink))))
 
     @classmethod
-    def thumbnail(cls, path, width, height=None, size="both", linear=False, crop="none"):
-        """vips_thumbnail() for JPEG and .v files: shrink-on-load, then the thumbnail_image pipeline."""
+    def thumbnail(cls, path, width, height=None, size="both", linear=False, crop="none", no_rotate=None):
+        """vips_thumbnail() for JPEG and .v files: shrink-on-load, then the thumbnail_image pipeline.
+        ``no_rotate=False`` undoes the file's orientation as vips_thumbnail does by default, ``True`` keeps the
+        pixels as stored and the tag on the result; ``None`` is the entry point without auto-rotation, which refuses
+        an oriented JPEG."""
         out = ctypes.c_void_p()
-        check(lib.vips_hip_thumbnail(os.fsencode(path), ctypes.byref(out), int(width), int(height) if height else 0,
-                                     _enum(SIZES, size, "size"), int(bool(linear)), _enum(INTERESTING, crop, "crop")))
+        args = (os.fsencode(path), ctypes.byref(out), int(width), int(height) if height else 0,
+                _enum(SIZES, size, "size"), int(bool(linear)), _enum(INTERESTING, crop, "crop"))
+        if no_rotate is None:
+            check(lib.vips_hip_thumbnail(*args))
+        else:
+            check(lib.vips_hip_thumbnail_rotate(*args, int(bool(no_rotate))))
         return cls(out.value)
 
     @classmethod
-    def thumbnail_batch(cls, paths, width, height=None, size="both", linear=False, crop="none", threads=8):
+    def thumbnail_batch(cls, paths, width, height=None, size="both", linear=False, crop="none", threads=8,
+                        no_rotate=None):
         """vips_thumbnail() over many files on `threads` host threads (decode and device work of
         different files overlap).  Returns a list of Images; a failed file gives a VipsHipError
         instance in its place."""
@@ -254,9 +280,12 @@ class Image(object):
         arr = (ctypes.c_char_p * n)(*[os.fsencode(p) for p in paths])
         outs = (ctypes.c_void_p * n)()
         errors = ctypes.create_string_buffer(256 * max(n, 1))
-        r = lib.vips_hip_thumbnail_batch(arr, n, outs, errors, int(width), int(height) if height else 0,
-                                         _enum(SIZES, size, "size"), int(bool(linear)),
-                                         _enum(INTERESTING, crop, "crop"), int(threads))
+        args = (arr, n, outs, errors, int(width), int(height) if height else 0, _enum(SIZES, size, "size"),
+                int(bool(linear)), _enum(INTERESTING, crop, "crop"))
+        if no_rotate is None:
+            r = lib.vips_hip_thumbnail_batch(*args, int(threads))
+        else:
+            r = lib.vips_hip_thumbnail_batch_rotate(*args, int(bool(no_rotate)), int(threads))
         if r < 0:
             check(r)
         result = []
@@ -267,9 +296,43 @@ class Image(object):
                 result.append(VipsHipError(errors.raw[256 * i:256 * i + 256].split(b"\0", 1)[0].decode()))
         return result
 
-    def thumbnail_image(self, width, height=None, size="both", linear=False, crop="none"):
-        return self._unary(lib.vips_hip_thumbnail_image_crop, int(width), int(height) if height else 0,
-                           _enum(SIZES, size, "size"), int(bool(linear)), _enum(INTERESTING, crop, "crop"))
+    def thumbnail_image(self, width, height=None, size="both", linear=False, crop="none", no_rotate=None):
+        args = (int(width), int(height) if height else 0, _enum(SIZES, size, "size"), int(bool(linear)),
+                _enum(INTERESTING, crop, "crop"))
+        if no_rotate is None:  # the entry point that does not look at the orientation
+            return self._unary(lib.vips_hip_thumbnail_image_crop, *args)
+        return self._unary(lib.vips_hip_thumbnail_image_rotate, *args, int(bool(no_rotate)))
+
+    # vips_rot / vips_flip / vips_autorot, with pyvips' names
+    def rot(self, angle):
+        return self._unary(lib.vips_hip_rot, _enum(ANGLES, angle, "angle"))
+
+    def rot90(self):
+        return self.rot("d90")
+
+    def rot180(self):
+        return self.rot("d180")
+
+    def rot270(self):
+        return self.rot("d270")
+
+    def flip(self, direction):
+        return self._unary(lib.vips_hip_flip, _enum(DIRECTIONS, direction, "direction"))
+
+    def fliphor(self):
+        return self.flip("horizontal")
+
+    def flipver(self):
+        return self.flip("vertical")
+
+    def autorot(self, with_options=False):
+        """Undo the orientation (one launch for a turn plus a flip); the result has none.  ``with_options``: also
+        return ``{"angle": "d90", "flip": False}``, the operation's optional outputs."""
+        angle, flip = ctypes.c_int(), ctypes.c_int()
+        out = self._unary(lib.vips_hip_autorot, ctypes.byref(angle), ctypes.byref(flip))
+        if with_options:
+            return out, {"angle": ANGLE_NAMES[angle.value], "flip": bool(flip.value)}
+        return out
 
     def extract_area(self, left, top, width, height):
         return self._unary(lib.vips_hip_extract_area, int(left), int(top), int(width), int(height))
