@@ -77,11 +77,12 @@ typedef enum {
 } VipsHipPrecision;
 
 /* The subset of VipsInterpretation (include/vips/image.h:94-118) the colour
- * path routes between; same values.
+ * path routes between, and HISTOGRAM, which vips_hip_hist_find's result carries; same values.
  */
 typedef enum {
 	VIPS_HIP_INTERPRETATION_MULTIBAND = 0,
 	VIPS_HIP_INTERPRETATION_B_W = 1,
+	VIPS_HIP_INTERPRETATION_HISTOGRAM = 10,
 	VIPS_HIP_INTERPRETATION_XYZ = 12,
 	VIPS_HIP_INTERPRETATION_LAB = 13,
 	VIPS_HIP_INTERPRETATION_LABS = 21,
@@ -626,8 +627,7 @@ VIPS_HIP_API int vips_hip_thumbnail_image(VipsHipImage *in, VipsHipImage **out,
 	int width, int height, int size, int linear);
 /* ... with the crop argument (a VipsInteresting, include/vips/conversion.h:97-107): the box is
  * filled instead of fitted (thumbnail.c:432-437) and the result cut to it by vips_smartcrop's
- * positional modes (conversion/smartcrop.c:359-400): 0 none, 1 centre, 4 low, 5 high, 6 all.
- * The content-driven modes (2 entropy, 3 attention) are refused.
+ * modes (vips_hip_smartcrop below): 0 none, 1 centre, 2 entropy, 3 attention, 4 low, 5 high, 6 all.
  */
 VIPS_HIP_API int vips_hip_thumbnail_image_crop(VipsHipImage *in, VipsHipImage **out,
 	int width, int height, int size, int linear, int crop);
@@ -643,6 +643,27 @@ VIPS_HIP_API int vips_hip_autorot(VipsHipImage *in, VipsHipImage **out, int *ang
 /* vips_extract_area (conversion/extract.c:137-187). */
 VIPS_HIP_API int vips_hip_extract_area(VipsHipImage *in, VipsHipImage **out,
 	int left, int top, int width, int height);
+/* vips_hist_find (arithmetic/hist_find.c) of a uchar image of 1 .. 4 bands: @band -1 counts every band, else
+ * the one band.  The result is a UINT image one row high, mx + 1 pels wide -- mx the largest value a counted
+ * band holds; 255 when every band is counted (hist_find.c:175-178, 350-394) -- of interpretation HISTOGRAM.
+ * Other formats (what the reference would cast) and images of 2^31 pels or more are refused. */
+VIPS_HIP_API int vips_hip_hist_find(VipsHipImage *in, VipsHipImage **out, int band);
+/* The kernel under it: the histograms of @n (1 .. 6) rectangles of @in -- @rects holds left, top, width, height
+ * for each -- in ONE launch and one copy back; @counts (host memory) takes 256 * bands counters a rectangle,
+ * the count of value v in band b at [v * bands + b].  vips_hip_hist_step: what the kernel takes at a time, for
+ * tests that want sizes round it (0: the bytes of a row a wave takes in a step; 1: the rows a block takes). */
+VIPS_HIP_API int vips_hip_hist_rects(VipsHipImage *in, const int *rects, int n, unsigned int *counts);
+VIPS_HIP_API int vips_hip_hist_step(int what);
+/* vips_smartcrop (conversion/smartcrop.c:322-437): @width x @height pels of @in, placed by @interesting (a
+ * VipsInteresting: 0 none, 1 centre, 2 entropy, 3 attention, 4 low, 5 high, 6 all).  @left, @top (where the
+ * crop was taken), @attention_x, @attention_y (the point the attention mode found; 0 for the others) may be NULL.
+ * entropy (smartcrop.c:106-176) takes uchar images of 1 or 3 bands: up to 8 rounds, each ONE launch of the
+ * histogram kernel over the six slices the round can ask about and one copy back; the slices' entropies
+ * (histogram/hist_entropy.c:61-95) are worked out on the host from the counters, step by step as the reference
+ * does.  attention (smartcrop.c:204-320) takes uchar images of 3 bands that vips_hip_colourspace takes to XYZ.
+ * Images with alpha, other formats and one-band attention are refused, with the mode's name in the message. */
+VIPS_HIP_API int vips_hip_smartcrop(VipsHipImage *in, VipsHipImage **out, int width, int height, int interesting,
+	int *left, int *top, int *attention_x, int *attention_y);
 VIPS_HIP_API int vips_hip_conv(VipsHipImage *in, VipsHipImage **out,
 	const double *mask, int mask_width, int mask_height, double scale, double offset,
 	int precision);

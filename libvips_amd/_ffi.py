@@ -255,6 +255,11 @@ _SIGNATURES = {
     "vips_hip_thumbnail_rotate": (c_int, [c_char_p, P(c_void_p), c_int, c_int, c_int, c_int, c_int, c_int]),
     "vips_hip_thumbnail_batch_rotate": (c_int, [P(c_char_p), c_int, P(c_void_p), c_char_p, c_int, c_int, c_int,
                                                 c_int, c_int, c_int, c_int]),
+    # histograms, smartcrop
+    "vips_hip_hist_find": (c_int, [c_void_p, P(c_void_p), c_int]),
+    "vips_hip_hist_rects": (c_int, [c_void_p, P(c_int), c_int, P(ctypes.c_uint)]),
+    "vips_hip_hist_step": (c_int, [c_int]),
+    "vips_hip_smartcrop": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, P(c_int), P(c_int), P(c_int), P(c_int)]),
     "vips_hip_premultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_unpremultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
 }

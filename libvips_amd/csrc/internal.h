@@ -56,6 +56,12 @@ struct ScopedStream {
 	bool saved_external, active;
 };
 
+// vips_hip_get_exact_float() is 1 on the calling thread while this lives (see runtime.cpp).
+struct ScopedExactFloat {
+	ScopedExactFloat();
+	~ScopedExactFloat();
+};
+
 // Kernel gates: VIPS_GATE_START/STOP analogue around a launch.
 struct Gate {
 	explicit Gate(const char *name);
@@ -155,4 +161,12 @@ int rot_op_gen(const char *domain, int op, const VipsHipRegion *in, const VipsHi
 // the operation vips_autorot runs for an orientation (autorot.c:119-160 folded: a turn and the flip behind it are
 // one operation here); 0 for orientations that change nothing
 int orientation_op(int orientation);
+// hist.hip: the histograms of n (1 .. HIST_MAX_RECTS) rectangles of a uchar image of 1 .. 4 bands, ONE launch.
+// Rectangle k's counts are ADDED to counters[k * 256 * bands + value * bands + band] (device memory, zero before
+// the first launch that uses them): the pel order of vips_hist_find's output.
+struct HistRect {
+	int left, top, width, height;
+};
+constexpr int HIST_MAX_RECTS = 6;
+int hist_rects(const char *domain, const _VipsHipImage *in, const HistRect *rects, int n, unsigned int *counters);
 } // namespace vh

@@ -1502,9 +1502,9 @@ int vips_hip_thumbnail_image(VipsHipImage *in, VipsHipImage **out, int width, in
 	return vips_hip_thumbnail_image_crop(in, out, width, height, size, linear, 0);
 }
 
-// ... with the crop argument: a VipsInteresting (include/vips/conversion.h:97-107).  The
-// positional modes are here (none 0, centre 1, low 4, high 5, all 6: smartcrop.c:359-400); the
-// content-driven ones (entropy 2, attention 3) are outside the path.
+// ... with the crop argument: a VipsInteresting (include/vips/conversion.h:97-107), which vips_hip_smartcrop
+// (smartcrop.cpp) carries out on the finished thumbnail: the positional modes (none 0, centre 1, low 4, high 5,
+// all 6) and the content-driven ones (entropy 2, attention 3) for the images it takes.
 //
 // @rotate: the orientation vips_autorot undoes between the conversion back to the output space and the crop
 // (thumbnail.c:989-1062), 0 or 1 for none.  One that swaps the axes (5 .. 8) swaps the target box for the shrink
@@ -1519,12 +1519,18 @@ static int thumbnail_image_any(VipsHipImage *in, VipsHipImage **out, int width, 
 		error(domain, "null argument");
 		return -1;
 	}
-	if (crop == 2 || crop == 3) {
-		error(domain, "crop modes 'entropy' and 'attention' are outside the HIP path");
-		return -1;
-	}
 	if (crop < 0 || crop > 6) {
 		error(domain, "bad crop mode %d", crop);
+		return -1;
+	}
+	// what vips_hip_smartcrop would refuse at the end whatever the pipeline does (the band count stays): now,
+	// before any kernel runs
+	if ((crop == 2 || crop == 3) && (in->bands == 2 || in->bands > 3)) {
+		error(domain, "crop mode '%s' does not take images with alpha", crop == 2 ? "entropy" : "attention");
+		return -1;
+	}
+	if (crop == 3 && in->bands < 3) {
+		error(domain, "crop mode 'attention' takes 3-band images (no B_W to XYZ route)");
 		return -1;
 	}
 	if (width <= 0) {
@@ -1644,24 +1650,11 @@ static int thumbnail_image_any(VipsHipImage *in, VipsHipImage **out, int width, 
 		vips_hip_image_unref(resized.im);
 		resized.im = upright.release();
 	}
-	if (crop != 0) { // thumbnail.c:1010-1038 -> vips_smartcrop's positional modes
+	if (crop != 0) { // thumbnail.c:1010-1038
 		const VipsHipImage *r = resized.im;
-		int crop_width = width < r->width ? width : r->width;
-		int crop_height = height < r->height ? height : r->height;
-		int left = 0, top = 0;
-		if (crop == 1) {
-			left = (r->width - crop_width) / 2;
-			top = (r->height - crop_height) / 2;
-		}
-		else if (crop == 5) {
-			left = r->width - crop_width;
-			top = r->height - crop_height;
-		}
-		else if (crop == 6) {
-			crop_width = r->width;
-			crop_height = r->height;
-		}
-		return vips_hip_extract_area(resized.im, out, left, top, crop_width, crop_height);
+		const int crop_width = width < r->width ? width : r->width;
+		const int crop_height = height < r->height ? height : r->height;
+		return vips_hip_smartcrop(resized.im, out, crop_width, crop_height, crop, nullptr, nullptr, nullptr, nullptr);
 	}
 	*out = resized.release();
 	return 0;

@@ -601,6 +601,14 @@ int vips_hip_vector_isenabled(void)
 
 // Float arithmetic mode.  -1 = not decided yet (first use reads $VIPS_HIP_EXACT_FLOAT).
 static std::atomic<int> g_exact_float(-1);
+// operations of the library that a DECISION hangs on (vips_hip_smartcrop's attention search: an arg-max) ask for the
+// reference's bits on their own thread while they run, whatever the process-wide mode is
+static thread_local int t_exact_float_scopes = 0;
+
+namespace vh {
+ScopedExactFloat::ScopedExactFloat() { t_exact_float_scopes++; }
+ScopedExactFloat::~ScopedExactFloat() { t_exact_float_scopes--; }
+} // namespace vh
 
 void vips_hip_set_exact_float(int enabled)
 {
@@ -609,6 +617,8 @@ void vips_hip_set_exact_float(int enabled)
 
 int vips_hip_get_exact_float(void)
 {
+	if (t_exact_float_scopes > 0)
+		return 1;
 	int v = g_exact_float.load();
 	if (v < 0) {
 		const char *env = getenv("VIPS_HIP_EXACT_FLOAT");

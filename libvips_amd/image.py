@@ -67,6 +67,7 @@ DIRECTIONS = {"horizontal": 0, "vertical": 1}
 INTERPRETATIONS = {
     "multiband": 0,
     "b-w": 1,
+    "histogram": 10,
     "xyz": 12,
     "lab": 13,
     "labs": 21,
@@ -338,6 +339,30 @@ class Image(object):
         return self._unary(lib.vips_hip_extract_area, int(left), int(top), int(width), int(height))
 
     crop = extract_area
+
+    def hist_find(self, band=-1):
+        """vips_hist_find of a uchar image: a uint image one row high, as wide as the largest counted value + 1
+        (256 when every band is counted), of interpretation histogram."""
+        return self._unary(lib.vips_hip_hist_find, int(band))
+
+    def hist_rects(self, rects):
+        """The histograms of up to six (left, top, width, height) rectangles in one launch of the histogram kernel:
+        an (n, 256, bands) uint32 array."""
+        n = len(rects)
+        flat = (ctypes.c_int * (4 * max(n, 1)))(*[int(v) for r in rects for v in r])
+        out = np.zeros((n, 256, self.bands), np.uint32)
+        check(lib.vips_hip_hist_rects(self._h, flat, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint))))
+        return out
+
+    def smartcrop(self, width, height, interesting="attention", with_options=False):
+        """vips_smartcrop.  ``with_options``: also return ``{"left", "top", "attention_x", "attention_y"}``: where
+        the crop was taken and, for the attention mode, the point it found."""
+        left, top, ax, ay = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        out = self._unary(lib.vips_hip_smartcrop, int(width), int(height), _enum(INTERESTING, interesting, "interesting"),
+                          ctypes.byref(left), ctypes.byref(top), ctypes.byref(ax), ctypes.byref(ay))
+        if with_options:
+            return out, {"left": left.value, "top": top.value, "attention_x": ax.value, "attention_y": ay.value}
+        return out
 
     @staticmethod
     def _mask(mask):
