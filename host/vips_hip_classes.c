@@ -1426,3 +1426,141 @@ static void
 vips_unpremultiply_hip_init(VipsUnpremultiplyHip *p)
 {
 }
+
+/* rank_hip / morph_hip: morphology/rank.c:541-587, morph.c:943-985.  Both have a region form in the C ABI
+ * (vips_hip_rank_gen, vips_hip_morph_gen: the edge copy is by whole-image coordinates), so an image over the HBM
+ * budget goes through in row strips; a strip reads the rows vips_hip_rank_need names -- half the window above, the
+ * rest below.  The original operation's build has checked the arguments by then (window too large, index out of
+ * range, bad mask element: hip_twin_header), in its own words. */
+typedef struct _VipsRankHip {
+	VipsHipOp parent_instance;
+	int width, height, index;
+} VipsRankHip;
+
+static int
+vips_rank_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsRankHip *rank = (VipsRankHip *) op;
+
+	return vips_hip_rank(in, out, rank->width, rank->height, rank->index);
+}
+
+static void
+vips_rank_hip_strip_close(VipsHipOp *op, void *plan)
+{
+}
+
+static int
+vips_rank_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	*plan = op; /* (the arguments are the plan) */
+
+	return 0;
+}
+
+static void
+vips_rank_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	vips_hip_rank_need(((VipsRankHip *) op)->height, out_top, out_rows, in_top, in_rows);
+}
+
+static int
+vips_rank_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsRankHip *rank = (VipsRankHip *) op;
+
+	return vips_hip_rank_gen(in, out, rank->width, rank->height, rank->index);
+}
+
+HIP_SUBCLASS_FULL(VipsRankHip, vips_rank_hip, "rank_hip", "rank filter (MI355X)", HIP_STRIPS(vips_rank_hip))
+
+static void
+vips_rank_hip_args(VipsRankHipClass *class)
+{
+	VIPS_ARG_INT(class, "width", 4, "Width", "Window width in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsRankHip, width), 1, 100000, 11);
+	VIPS_ARG_INT(class, "height", 5, "Height", "Window height in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsRankHip, height), 1, 100000, 11);
+	VIPS_ARG_INT(class, "index", 6, "Index", "Select pixel at index",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsRankHip, index), 0, 100000000, 50);
+}
+
+static void
+vips_rank_hip_init(VipsRankHip *rank)
+{
+	rank->width = 11;
+	rank->height = 11;
+	rank->index = 50;
+}
+
+typedef struct _VipsMorphHip {
+	VipsHipOp parent_instance;
+	VipsImage *mask;
+	VipsOperationMorphology morph;
+} VipsMorphHip;
+
+static int
+vips_morph_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsMorphHip *morph = (VipsMorphHip *) op;
+	VipsImage *M;
+	int result;
+
+	if (vips_check_matrix("morph_hip", morph->mask, &M))
+		return -1;
+	result = vips_hip_morph(in, out, VIPS_MATRIX(M, 0, 0), M->Xsize, M->Ysize, morph->morph);
+	g_object_unref(M);
+
+	return result;
+}
+
+static void
+vips_morph_hip_strip_close(VipsHipOp *op, void *plan)
+{
+	VIPS_UNREF(plan);
+}
+
+/* the plan is the mask as a matrix image */
+static int
+vips_morph_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	VipsImage *M;
+
+	if (vips_check_matrix("morph_hip", ((VipsMorphHip *) op)->mask, &M))
+		return -1;
+	*plan = M;
+
+	return 0;
+}
+
+static void
+vips_morph_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	vips_hip_rank_need(((VipsImage *) plan)->Ysize, out_top, out_rows, in_top, in_rows);
+}
+
+static int
+vips_morph_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsImage *M = (VipsImage *) plan;
+
+	return vips_hip_morph_gen(in, out, VIPS_MATRIX(M, 0, 0), M->Xsize, M->Ysize, ((VipsMorphHip *) op)->morph);
+}
+
+HIP_SUBCLASS_FULL(VipsMorphHip, vips_morph_hip, "morph_hip", "morphology operation (MI355X)", HIP_STRIPS(vips_morph_hip))
+
+static void
+vips_morph_hip_args(VipsMorphHipClass *class)
+{
+	VIPS_ARG_IMAGE(class, "mask", 20, "Mask", "Input matrix image",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsMorphHip, mask));
+	VIPS_ARG_ENUM(class, "morph", 103, "Morphology", "Morphological operation to perform",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsMorphHip, morph),
+		VIPS_TYPE_OPERATION_MORPHOLOGY, VIPS_OPERATION_MORPHOLOGY_ERODE);
+}
+
+static void
+vips_morph_hip_init(VipsMorphHip *morph)
+{
+	morph->morph = VIPS_OPERATION_MORPHOLOGY_ERODE;
+}

@@ -1547,7 +1547,8 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *   - thumbnail_image of images with fewer than 3 bands other than one-band uchar B_W, not linear -- grey +
  *     alpha, GREY16, linear one-band (resample/thumbnail.c:806-820) -- and with the content-driven crops
  *     (entropy, attention: conversion/smartcrop.c);
- *   - rot / flip / autorot of an image over the HBM budget (they have no strip form).
+ *   - rot / flip / autorot of an image over the HBM budget (they have no strip form);
+ *   - rank of double images (the device kernels sort keys of at most 32 bits).
  */
 static gboolean
 hip_wants_original(VipsHipOp *op, VipsImage *in)
@@ -1563,6 +1564,8 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 	 * image that does not fit the HBM budget beside its result is the original's */
 	if ((strcmp(nick, "rot_hip") == 0 || strcmp(nick, "flip_hip") == 0 || strcmp(nick, "autorot_hip") == 0) &&
 		2 * (guint64) VIPS_IMAGE_SIZEOF_IMAGE(in) > hip_budget())
+		return TRUE;
+	if (strcmp(nick, "rank_hip") == 0 && in->BandFmt == VIPS_FORMAT_DOUBLE)
 		return TRUE;
 	if (strcmp(nick, "thumbnail_image_hip") == 0) {
 		gboolean linear = FALSE;
@@ -1697,7 +1700,7 @@ vips_hip_op_init(VipsHipOp *op)
 
 /* ------------------------------------------------------------------ subclasses */
 
-/* (the 20 operation classes: arguments, defaults, hooks) */
+/* (the 22 operation classes: arguments, defaults, hooks) */
 #include "vips_hip_classes.c"
 
 /* ------------------------------------------------------------------ registration */
@@ -1728,6 +1731,8 @@ g_module_check_init(GModule *module)
 	vips_autorot_hip_get_type();
 	vips_premultiply_hip_get_type();
 	vips_unpremultiply_hip_get_type();
+	vips_rank_hip_get_type();
+	vips_morph_hip_get_type();
 
 	/* types registered by a module must never be unloaded */
 	g_module_make_resident(module);

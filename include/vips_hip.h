@@ -474,6 +474,39 @@ VIPS_HIP_API int vips_hip_rot_gen(int angle, const VipsHipRegion *in, const Vips
 VIPS_HIP_API int vips_hip_flip_gen(int direction, const VipsHipRegion *in, const VipsHipRegion *out);
 VIPS_HIP_API int vips_hip_rot_tile_side(int pel_size);
 
+/* ----------------------------------------------------------------- morphology
+ *
+ * vips_rank_generate (morphology/rank.c:412-456): out element (x, y, b) is the @index-th smallest (from 0) of the
+ * @width x @height window whose top-left is input pel (x - width / 2, y - height / 2), band b, pel coordinates clamped
+ * to the image (the embed of rank.c:507-511).  uchar, char, ushort, short, uint, int and float; the output has the
+ * input's format.  Errors with the reference's words: "window too large" (width > im_width or height > im_height),
+ * "index out of range".  double images are refused.  Float results are defined for inputs without NaN (the
+ * reference's own answer depends on which of its four routes runs) and compare equal by value: -0 sorts below +0.
+ * Three kernels: rank_median3 (3 x 3, index 4), rank_minmax (index 0 or n - 1, separable), rank_select (the rest:
+ * bisection on an order-preserving key).  The window is limited by the kernels' LDS only: 8 + height - 1 staged rows
+ * of 256 + (width - 1) * bands elements -- and as many rows of 256 more for rank_minmax -- must fit a CU's 160 KB;
+ * 31 x 31 fits for every format up to 16 bands, what does not fit is refused with the sizes in the message.
+ *
+ * vips_erode_gen / vips_dilate_gen (morph.c:662-826): @mask is mask_width x mask_height doubles of 0, 128 and 255
+ * (after rint(); anything else: "bad mask element (%f should be 0, 128 or 255)"), origin (mask_width / 2,
+ * mask_height / 2); @morph is a VipsOperationMorphology (0 erode, 1 dilate).  The loops are over ELEMENTS and
+ * bitwise: dilate ORs, erode ANDs, over the mask positions that are not 128, the input byte (255) or its complement
+ * (0).  The input may have any non-complex format: it is vips_cast to uchar first (morph.c:866-870); the output is
+ * uchar.  Masks up to 32 x 32 whose tile fits a CU's 160 KB of LDS (16 + mask_height - 1 rows of 1024 + (mask_width
+ * - 1) * bands bytes: every mask up to 76 bands); others are refused.
+ *
+ * Both read, for output rows top .. top + height - 1, the input rows vips_hip_rank_need() names -- window_height / 2
+ * above, the rest of the window below -- before they are clipped to the image (for vips_hip_morph_gen:
+ * window_height = mask_height).  vips_hip_rank_step: the tiles of the kernels, for tests that want sizes round them
+ * (0 / 1: elements of a row / rows a block of the rank kernels makes; 2 / 3: of the morph kernels; 4: the largest
+ * mask side of vips_hip_morph_gen).
+ */
+VIPS_HIP_API int vips_hip_rank_gen(const VipsHipRegion *in, const VipsHipRegion *out, int width, int height, int index);
+VIPS_HIP_API int vips_hip_morph_gen(const VipsHipRegion *in, const VipsHipRegion *out,
+	const double *mask, int mask_width, int mask_height, int morph);
+VIPS_HIP_API void vips_hip_rank_need(int window_height, int top, int height, int *in_top, int *in_height);
+VIPS_HIP_API int vips_hip_rank_step(int what);
+
 /* vips_sharpen_generate (convolution/sharpen.c:116-168): LabS in, LabS out; the
  * blurred L band comes from a vips_hip_conv_gen pass the caller ran.
  */
@@ -664,6 +697,13 @@ VIPS_HIP_API int vips_hip_hist_step(int what);
  * Images with alpha, other formats and one-band attention are refused, with the mode's name in the message. */
 VIPS_HIP_API int vips_hip_smartcrop(VipsHipImage *in, VipsHipImage **out, int width, int height, int interesting,
 	int *left, int *top, int *attention_x, int *attention_y);
+/* vips_rank (morphology/rank.c:458-539), vips_median (:639-671: rank(size, size, size * size / 2)) and vips_morph
+ * (morph.c:828-941) on whole images: see vips_hip_rank_gen / vips_hip_morph_gen above for what they compute, take and
+ * refuse.  The result has the size of the input; vips_hip_morph's is uchar. */
+VIPS_HIP_API int vips_hip_rank(VipsHipImage *in, VipsHipImage **out, int width, int height, int index);
+VIPS_HIP_API int vips_hip_median(VipsHipImage *in, VipsHipImage **out, int size);
+VIPS_HIP_API int vips_hip_morph(VipsHipImage *in, VipsHipImage **out,
+	const double *mask, int mask_width, int mask_height, int morph);
 VIPS_HIP_API int vips_hip_conv(VipsHipImage *in, VipsHipImage **out,
 	const double *mask, int mask_width, int mask_height, double scale, double offset,
 	int precision);

@@ -260,6 +260,14 @@ _SIGNATURES = {
     "vips_hip_hist_rects": (c_int, [c_void_p, P(c_int), c_int, P(ctypes.c_uint)]),
     "vips_hip_hist_step": (c_int, [c_int]),
     "vips_hip_smartcrop": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, P(c_int), P(c_int), P(c_int), P(c_int)]),
+    # rank / median / morph
+    "vips_hip_rank_gen": (c_int, [RegionP, RegionP, c_int, c_int, c_int]),
+    "vips_hip_morph_gen": (c_int, [RegionP, RegionP, P(c_double), c_int, c_int, c_int]),
+    "vips_hip_rank_need": (None, [c_int, c_int, c_int, P(c_int), P(c_int)]),
+    "vips_hip_rank_step": (c_int, [c_int]),
+    "vips_hip_rank": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int]),
+    "vips_hip_median": (c_int, [c_void_p, P(c_void_p), c_int]),
+    "vips_hip_morph": (c_int, [c_void_p, P(c_void_p), P(c_double), c_int, c_int, c_int]),
     "vips_hip_premultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_unpremultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
 }

@@ -169,4 +169,24 @@ struct HistRect {
 };
 constexpr int HIST_MAX_RECTS = 6;
 int hist_rects(const char *domain, const _VipsHipImage *in, const HistRect *rects, int n, unsigned int *counters);
+// rank.hip, morph.hip: the neighbourhood filters on checked regions (ops_morphology.cpp checks them and fills the
+// geometry of NbArgs, nbhd_tile.h; the kernels' files set the rest).  `mask` holds 0, 128 and 255.  *_tile: 0 the
+// elements of a row a block makes, 1 its rows (morph_tile 2: the largest mask side).
+struct NbArgs {
+	const unsigned char *in;
+	unsigned char *out;
+	long long in_stride, out_stride;          // bytes
+	int in_left, in_top, in_width, in_height; // the input window, pels of the whole image
+	int im_width, im_height;
+	int out_left, out_top, out_width, out_height; // `out` points at pel (out_left, out_top)
+	int bands;        // elements a pel
+	int win_w, win_h; // the neighbourhood, pels; its origin is (win_w / 2, win_h / 2)
+	int lds_row;      // bytes of a staged row, a multiple of 16
+	int index;        // rank: the index-th smallest
+	unsigned int key_xor;
+};
+int rank_run(const char *domain, NbArgs a, int format);
+int morph_run(const char *domain, NbArgs a, const unsigned char *mask, int dilate);
+int rank_tile(int what);
+int morph_tile(int what);
 } // namespace vh

@@ -63,6 +63,8 @@ INTERESTING = {"none": 0, "centre": 1, "entropy": 2, "attention": 3, "low": 4, "
 ANGLES = {"d0": 0, "d90": 1, "d180": 2, "d270": 3}
 ANGLE_NAMES = {v: k for k, v in ANGLES.items()}
 DIRECTIONS = {"horizontal": 0, "vertical": 1}
+# VipsOperationMorphology (include/vips/morphology.h)
+MORPHOLOGIES = {"erode": 0, "dilate": 1}
 # VipsInterpretation (include/vips/image.h:94-118)
 INTERPRETATIONS = {
     "multiband": 0,
@@ -363,6 +365,20 @@ class Image(object):
         if with_options:
             return out, {"left": left.value, "top": top.value, "attention_x": ax.value, "attention_y": ay.value}
         return out
+
+    # vips_rank / vips_median / vips_morph
+    def rank(self, width, height, index):
+        """The ``index``-th smallest (from 0) of every ``width`` x ``height`` window, band by band, edges copied."""
+        return self._unary(lib.vips_hip_rank, int(width), int(height), int(index))
+
+    def median(self, size=3):
+        return self._unary(lib.vips_hip_median, int(size))
+
+    def morph(self, mask, morph):
+        """Erode or dilate by a mask (a nested list or array) of 0, 128 and 255; the result is uchar."""
+        m = self._mask(mask)
+        return self._unary(lib.vips_hip_morph, m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), m.shape[1], m.shape[0],
+                           _enum(MORPHOLOGIES, morph, "morph"))
 
     @staticmethod
     def _mask(mask):
