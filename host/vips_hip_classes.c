@@ -1564,3 +1564,276 @@ vips_morph_hip_init(VipsMorphHip *morph)
 {
 	morph->morph = VIPS_OPERATION_MORPHOLOGY_ERODE;
 }
+
+/* affine_hip / similarity_hip / rotate_hip: resample/affine.c:627-718, similarity.c:113-300.  One instance struct for
+ * the three (similarity and rotate make their matrix, similarity.c:89-92).  The original operation's build has checked
+ * the arguments by then and gives the header; the plan of the C ABI (vips_hip_affine_plan_new) restates it without
+ * touching a pixel.  In row strips above the HBM budget: a strip's input rows are vips_hip_affine_need of its rect.
+ * For an image with alpha that is not premultiplied a strip is the chain premultiply -> affine -> unpremultiply -> cast
+ * on its window.
+ * What the device refuses -- double and complex images, the other interpolators, pels over 64 bytes -- is the
+ * original's (hip_wants_original). */
+typedef struct _VipsAffineHip {
+	VipsHipOp parent_instance;
+	VipsArrayDouble *matrix;
+	double scale, angle;
+	VipsInterpolate *interpolate;
+	VipsArrayInt *oarea;
+	double odx, ody, idx, idy;
+	VipsArrayDouble *background;
+	gboolean premultiplied;
+	VipsExtend extend;
+} VipsAffineHip;
+typedef VipsAffineHip VipsSimilarityHip;
+typedef VipsAffineHip VipsRotateHip;
+
+/* -1: an interpolator the device does not have */
+static int
+affine_hip_interpolator(VipsInterpolate *interpolate)
+{
+	const char *nick = interpolate ? VIPS_OBJECT_GET_CLASS(interpolate)->nickname : "bilinear";
+
+	return strcmp(nick, "nearest") == 0 ? VIPS_HIP_INTERPOLATE_NEAREST
+		: strcmp(nick, "bilinear") == 0 ? VIPS_HIP_INTERPOLATE_BILINEAR
+		: strcmp(nick, "bicubic") == 0  ? VIPS_HIP_INTERPOLATE_BICUBIC
+										: -1;
+}
+
+static int
+affine_hip_arguments(VipsHipOp *op, VipsHipAffine *a)
+{
+	const char *nick = VIPS_OBJECT_GET_CLASS(op)->nickname;
+	VipsAffineHip *affine = (VipsAffineHip *) op;
+
+	vips_hip_affine_defaults(a);
+	if (strcmp(nick, "affine_hip") == 0) {
+		int n;
+		const double *m = vips_array_double_get(affine->matrix, &n);
+
+		if (n != 4) {
+			vips_error(nick, "%s", "vector must have 4 elements");
+			return -1;
+		}
+		a->a = m[0];
+		a->b = m[1];
+		a->c = m[2];
+		a->d = m[3];
+		a->extend = affine->extend;
+		a->premultiplied = affine->premultiplied;
+		if (vips_object_argument_isset(VIPS_OBJECT(op), "oarea")) {
+			const int *r = vips_array_int_get(affine->oarea, &n);
+
+			if (n != 4) {
+				vips_error(nick, "%s", "vector must have 4 elements");
+				return -1;
+			}
+			memcpy(a->oarea, r, 4 * sizeof(int));
+			a->have_oarea = 1;
+		}
+	}
+	else {
+		const double rad = VIPS_RAD(affine->angle);
+
+		a->a = affine->scale * cos(rad);
+		a->b = affine->scale * -sin(rad);
+		a->c = -a->b;
+		a->d = a->a;
+	}
+	a->interpolate = affine_hip_interpolator(affine->interpolate);
+	a->odx = affine->odx;
+	a->ody = affine->ody;
+	a->idx = affine->idx;
+	a->idy = affine->idy;
+	if (affine->background) {
+		int n;
+		const double *v = vips_array_double_get(affine->background, &n);
+
+		if (n > VIPS_HIP_AFFINE_MAX_BACKGROUND) {
+			vips_error(nick, "%s", "background too long");
+			return -1;
+		}
+		a->n_background = n;
+		memcpy(a->background, v, n * sizeof(double));
+	}
+	/* the hint of a pipeline is the smallest of its inputs' (iofuncs/image.c): a tiled input makes the affine tiled */
+	a->force_tiles = op->ready && op->ready->dhint == VIPS_DEMAND_STYLE_SMALLTILE;
+
+	return 0;
+}
+
+static int
+vips_affine_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsHipAffine a;
+
+	if (affine_hip_arguments(op, &a))
+		return -1;
+
+	return vips_hip_affine(in, out, &a);
+}
+
+static void
+vips_affine_hip_strip_close(VipsHipOp *op, void *plan)
+{
+	vips_hip_affine_plan_free((VipsHipAffinePlan *) plan);
+}
+
+static int
+vips_affine_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	VipsHipAffine a;
+	VipsHipAffinePlan *p;
+
+	if (affine_hip_arguments(op, &a))
+		return -1;
+	if (!(p = vips_hip_affine_plan_new(&a, in->Xsize, in->Ysize, in->Bands, in->BandFmt, in->Type)))
+		return hip_fail(VIPS_OBJECT_GET_CLASS(op)->nickname);
+	/* the copy has no region form */
+	if (vips_hip_affine_plan_get(p, 2)) {
+		vips_hip_affine_plan_free(p);
+		return 1;
+	}
+	*plan = p;
+
+	return 0;
+}
+
+static void
+vips_affine_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	int need[4];
+
+	vips_hip_affine_need((VipsHipAffinePlan *) plan, 0, out_top, op->out->Xsize, out_rows, need);
+	/* (a strip of nothing but background reads no row: any one will do) */
+	*in_top = need[3] > 0 ? need[1] : 0;
+	*in_rows = need[3] > 0 ? need[3] : 1;
+}
+
+static int
+vips_affine_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsHipAffinePlan *p = (VipsHipAffinePlan *) plan;
+	const int tile = vips_hip_affine_plan_get(p, 3);
+	const double max_alpha = vips_interpretation_max_alpha(op->ready->Type);
+	VipsHipImage *tmp[3] = { NULL, NULL, NULL };
+	VipsHipRegion pre, made, un;
+	int result = -1;
+
+	if (!vips_hip_affine_plan_get(p, 4))
+		return vips_hip_affine_gen(p, in, out, tile);
+
+	/* alpha, not premultiplied (affine.c:546-563, :614-619): the window premultiplied to float, the strip resampled
+	 * from that, unpremultiplied and cast back -- three device images that live as long as this call's launches */
+	if ((tmp[0] = vips_hip_image_new(in->width, in->height, in->bands, VIPS_HIP_FORMAT_FLOAT, 0)) &&
+		(tmp[1] = vips_hip_image_new(out->width, out->height, out->bands, VIPS_HIP_FORMAT_FLOAT, 0)) &&
+		(tmp[2] = vips_hip_image_new(out->width, out->height, out->bands, VIPS_HIP_FORMAT_FLOAT, 0))) {
+		vips_hip_image_region(tmp[0], &pre);
+		pre.left = in->left;
+		pre.top = in->top;
+		pre.im_width = in->im_width;
+		pre.im_height = in->im_height;
+		vips_hip_image_region(tmp[1], &made);
+		vips_hip_image_region(tmp[2], &un);
+		made.left = un.left = out->left;
+		made.top = un.top = out->top;
+		made.im_width = un.im_width = out->im_width;
+		made.im_height = un.im_height = out->im_height;
+		if (!vips_hip_premultiply_gen(in, &pre, max_alpha, 0, 0) &&
+			!vips_hip_affine_gen(p, &pre, &made, tile) &&
+			!vips_hip_premultiply_gen(&made, &un, max_alpha, 0, 1) &&
+			!vips_hip_cast_gen(&un, out))
+			result = 0;
+	}
+	for (int i = 0; i < 3; i++)
+		if (tmp[i])
+			vips_hip_image_unref(tmp[i]);
+
+	return result;
+}
+
+#define vips_similarity_hip_compute vips_affine_hip_compute
+#define vips_similarity_hip_strip_open vips_affine_hip_strip_open
+#define vips_similarity_hip_strip_need vips_affine_hip_strip_need
+#define vips_similarity_hip_strip_run vips_affine_hip_strip_run
+#define vips_similarity_hip_strip_close vips_affine_hip_strip_close
+#define vips_rotate_hip_compute vips_affine_hip_compute
+#define vips_rotate_hip_strip_open vips_affine_hip_strip_open
+#define vips_rotate_hip_strip_need vips_affine_hip_strip_need
+#define vips_rotate_hip_strip_run vips_affine_hip_strip_run
+#define vips_rotate_hip_strip_close vips_affine_hip_strip_close
+
+HIP_SUBCLASS_FULL(VipsAffineHip, vips_affine_hip, "affine_hip", "affine transform of an image (MI355X)", HIP_STRIPS(vips_affine_hip))
+HIP_SUBCLASS_FULL(VipsSimilarityHip, vips_similarity_hip, "similarity_hip", "similarity transform of an image (MI355X)",
+	HIP_STRIPS(vips_similarity_hip))
+HIP_SUBCLASS_FULL(VipsRotateHip, vips_rotate_hip, "rotate_hip", "rotate an image by a number of degrees (MI355X)",
+	HIP_STRIPS(vips_rotate_hip))
+
+/* what the three share: the interpolator, the background, the four displacements */
+static void
+affine_hip_common_args(VipsHipOpClass *class, int interpolate_priority, int background_priority)
+{
+	VIPS_ARG_INTERPOLATE(class, "interpolate", interpolate_priority, "Interpolate", "Interpolate pixels with this",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, interpolate));
+	VIPS_ARG_BOXED(class, "background", background_priority, "Background", "Background value",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, background), VIPS_TYPE_ARRAY_DOUBLE);
+	VIPS_ARG_DOUBLE(class, "odx", 112, "Output offset", "Horizontal output displacement",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, odx), -10000000, 10000000, 0);
+	VIPS_ARG_DOUBLE(class, "ody", 113, "Output offset", "Vertical output displacement",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, ody), -10000000, 10000000, 0);
+	VIPS_ARG_DOUBLE(class, "idx", 114, "Input offset", "Horizontal input displacement",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, idx), -10000000, 10000000, 0);
+	VIPS_ARG_DOUBLE(class, "idy", 115, "Input offset", "Vertical input displacement",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, idy), -10000000, 10000000, 0);
+}
+
+static void
+vips_affine_hip_args(VipsAffineHipClass *class)
+{
+	VIPS_ARG_BOXED(class, "matrix", 110, "Matrix", "Transformation matrix",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsAffineHip, matrix), VIPS_TYPE_ARRAY_DOUBLE);
+	affine_hip_common_args(class, 2, 116);
+	VIPS_ARG_BOXED(class, "oarea", 111, "Output rect", "Area of output to generate",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, oarea), VIPS_TYPE_ARRAY_INT);
+	VIPS_ARG_ENUM(class, "extend", 117, "Extend", "How to generate the extra pixels",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, extend), VIPS_TYPE_EXTEND, VIPS_EXTEND_BACKGROUND);
+	VIPS_ARG_BOOL(class, "premultiplied", 117, "Premultiplied", "Images have premultiplied alpha",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, premultiplied), FALSE);
+}
+
+static void
+vips_similarity_hip_args(VipsSimilarityHipClass *class)
+{
+	VIPS_ARG_DOUBLE(class, "scale", 3, "Scale", "Scale by this factor",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, scale), 0, 10000000, 1);
+	VIPS_ARG_DOUBLE(class, "angle", 4, "Angle", "Rotate clockwise by this many degrees",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsAffineHip, angle), -10000000, 10000000, 0);
+	affine_hip_common_args(class, 5, 6);
+}
+
+static void
+vips_rotate_hip_args(VipsRotateHipClass *class)
+{
+	VIPS_ARG_DOUBLE(class, "angle", 4, "Angle", "Rotate clockwise by this many degrees",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsAffineHip, angle), -10000000, 10000000, 0);
+	affine_hip_common_args(class, 5, 6);
+}
+
+static void
+vips_affine_hip_init(VipsAffineHip *affine)
+{
+	affine->scale = 1;
+	affine->extend = VIPS_EXTEND_BACKGROUND;
+	affine->background = vips_array_double_newv(1, 0.0);
+}
+
+static void
+vips_similarity_hip_init(VipsSimilarityHip *affine)
+{
+	vips_affine_hip_init(affine);
+}
+
+static void
+vips_rotate_hip_init(VipsRotateHip *affine)
+{
+	vips_affine_hip_init(affine);
+}

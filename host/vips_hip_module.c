@@ -1548,7 +1548,9 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *     alpha, GREY16, linear one-band (resample/thumbnail.c:806-820) -- and with the content-driven crops
  *     (entropy, attention: conversion/smartcrop.c);
  *   - rot / flip / autorot of an image over the HBM budget (they have no strip form);
- *   - rank of double images (the device kernels sort keys of at most 32 bits).
+ *   - rank of double images (the device kernels sort keys of at most 32 bits);
+ *   - affine / similarity / rotate of double images, with an interpolator other than nearest, bilinear and bicubic
+ *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands.
  */
 static gboolean
 hip_wants_original(VipsHipOp *op, VipsImage *in)
@@ -1567,6 +1569,21 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 		return TRUE;
 	if (strcmp(nick, "rank_hip") == 0 && in->BandFmt == VIPS_FORMAT_DOUBLE)
 		return TRUE;
+	if (strcmp(nick, "affine_hip") == 0 || strcmp(nick, "similarity_hip") == 0 || strcmp(nick, "rotate_hip") == 0) {
+		VipsInterpolate *interpolate = NULL;
+		gboolean other = FALSE;
+
+		g_object_get(op, "interpolate", &interpolate, NULL);
+		if (interpolate) {
+			const char *name = VIPS_OBJECT_GET_CLASS(interpolate)->nickname;
+
+			other = strcmp(name, "nearest") != 0 && strcmp(name, "bilinear") != 0 && strcmp(name, "bicubic") != 0;
+			g_object_unref(interpolate);
+		}
+		/* (a pel of the premultiplied float image may be four bytes a band) */
+		if (other || in->BandFmt == VIPS_FORMAT_DOUBLE || in->Bands * 4 > VIPS_HIP_AFFINE_MAX_PEL)
+			return TRUE;
+	}
 	if (strcmp(nick, "thumbnail_image_hip") == 0) {
 		gboolean linear = FALSE;
 		int crop = 0;
@@ -1700,7 +1717,7 @@ vips_hip_op_init(VipsHipOp *op)
 
 /* ------------------------------------------------------------------ subclasses */
 
-/* (the 22 operation classes: arguments, defaults, hooks) */
+/* (the 25 operation classes: arguments, defaults, hooks) */
 #include "vips_hip_classes.c"
 
 /* ------------------------------------------------------------------ registration */
@@ -1733,6 +1750,9 @@ g_module_check_init(GModule *module)
 	vips_unpremultiply_hip_get_type();
 	vips_rank_hip_get_type();
 	vips_morph_hip_get_type();
+	vips_affine_hip_get_type();
+	vips_similarity_hip_get_type();
+	vips_rotate_hip_get_type();
 
 	/* types registered by a module must never be unloaded */
 	g_module_make_resident(module);

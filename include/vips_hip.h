@@ -783,6 +783,72 @@ VIPS_HIP_API int vips_hip_cast(VipsHipImage *in, VipsHipImage **out, int format)
 VIPS_HIP_API int vips_hip_premultiply(VipsHipImage *in, VipsHipImage **out, int uchar);
 VIPS_HIP_API int vips_hip_unpremultiply(VipsHipImage *in, VipsHipImage **out, int uchar);
 
+/* ------------------------------------------------ affine / similarity / rotate
+ *
+ * vips_affine (resample/affine.c:226-625) with the nearest / bilinear / bicubic interpolators, any matrix, every
+ * `extend`, `background`, `oarea`, `odx` / `ody` / `idx` / `idy` and `premultiplied`; vips_similarity and vips_rotate
+ * (resample/similarity.c:83-111) make their matrix and run it.  uchar ... int and float images of pels up to
+ * VIPS_HIP_AFFINE_MAX_PEL bytes; double and complex images and every other interpolator are refused by name.
+ */
+typedef enum { /* VipsExtend, include/vips/conversion.h */
+	VIPS_HIP_EXTEND_BLACK = 0,
+	VIPS_HIP_EXTEND_COPY = 1,
+	VIPS_HIP_EXTEND_REPEAT = 2,
+	VIPS_HIP_EXTEND_MIRROR = 3,
+	VIPS_HIP_EXTEND_WHITE = 4,
+	VIPS_HIP_EXTEND_BACKGROUND = 5
+} VipsHipExtend;
+
+#define VIPS_HIP_AFFINE_MAX_PEL 64
+#define VIPS_HIP_AFFINE_MAX_BACKGROUND 64
+
+/* The arguments of vips_affine.  vips_hip_affine_defaults() sets the operation's defaults: the identity matrix,
+ * bilinear, extend background, background 0, no oarea (the bounding box of the transformed image is used). */
+typedef struct {
+	double a, b, c, d;
+	double odx, ody, idx, idy;
+	int oarea[4]; /* left, top, width, height */
+	int have_oarea;
+	int interpolate; /* VipsHipInterpolate; any other value is refused */
+	int extend;      /* VipsHipExtend */
+	int premultiplied;
+	int force_tiles;  /* the input comes from a SMALLTILE pipeline: 128-column rects even for a pure scale */
+	int n_background; /* 1 or the band count */
+	double background[VIPS_HIP_AFFINE_MAX_BACKGROUND];
+} VipsHipAffine;
+VIPS_HIP_API void vips_hip_affine_defaults(VipsHipAffine *args);
+
+/* vips_affine_build restated for an input image of the given header: the inverse ("singular or near-singular
+ * matrix"), the default oarea, the identity shortcut, the range check ("output coordinates out of range"), the ink
+ * ("linear: vector must have 1 or N elements").  No pixel moves and no device is touched.  An image with alpha (by
+ * its interpretation and bands, vips_image_hasalpha) and premultiplied == 0 is resampled as the float image
+ * vips_premultiply makes of it: the plan's regions are then float.
+ * vips_hip_affine_plan_get: 0 / 1 output width / height, 2 the transform is the identity copy, 3 the rect grid the
+ * reference's demand hint gives for an image from memory (0: whole rows, b == c == 0 and an extend other than repeat
+ * and mirror, whose embed is tiled; else 128), 4 the regions are the premultiplied float
+ * image's, 5 the format of the regions. */
+typedef struct _VipsHipAffinePlan VipsHipAffinePlan;
+VIPS_HIP_API VipsHipAffinePlan *vips_hip_affine_plan_new(const VipsHipAffine *args, int width, int height, int bands,
+	int format, int interpretation);
+VIPS_HIP_API void vips_hip_affine_plan_free(VipsHipAffinePlan *plan);
+VIPS_HIP_API int vips_hip_affine_plan_get(const VipsHipAffinePlan *plan, int what);
+/* The rect of the input image that the output rect (left, top, width, height) reads (affine.c:267-303), clipped to
+ * the image; in[2] or in[3] is 0 when the rect is all background. */
+VIPS_HIP_API void vips_hip_affine_need(const VipsHipAffinePlan *plan, int left, int top, int width, int height, int in[4]);
+/* vips_affine_gen (affine.c:226-410): fills @out's rect of the output image from @in, a window of the (premultiplied)
+ * input image that must cover vips_hip_affine_need() of the rect ("input region too small" otherwise; for an
+ * all-background rect any window will do).  The reference accumulates a row's coordinates from the first pixel of
+ * each generate rect: @tile_width says where those rects start (multiples of it on the output image's own grid, up
+ * to 1024; 0 = whole rows, which needs b == c == 0).  The accumulation is replayed on the device, add by add. */
+VIPS_HIP_API int vips_hip_affine_gen(VipsHipAffinePlan *plan, const VipsHipRegion *in, const VipsHipRegion *out,
+	int tile_width);
+/* Whole images; the premultiply / unpremultiply / cast chain of affine.c:546-619 included. */
+VIPS_HIP_API int vips_hip_affine(VipsHipImage *in, VipsHipImage **out, const VipsHipAffine *args);
+/* @args: everything but the matrix (NULL: the defaults). */
+VIPS_HIP_API int vips_hip_similarity(VipsHipImage *in, VipsHipImage **out, double scale, double angle,
+	const VipsHipAffine *args);
+VIPS_HIP_API int vips_hip_rotate(VipsHipImage *in, VipsHipImage **out, double angle, const VipsHipAffine *args);
+
 #ifdef __cplusplus
 }
 #endif

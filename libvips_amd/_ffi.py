@@ -69,6 +69,24 @@ class JpegHeader(ctypes.Structure):
     ]
 
 
+class Affine(ctypes.Structure):
+    """VipsHipAffine (include/vips_hip.h): the arguments of vips_affine."""
+
+    MAX_BACKGROUND = 64
+    _fields_ = [
+        ("a", ctypes.c_double), ("b", ctypes.c_double), ("c", ctypes.c_double), ("d", ctypes.c_double),
+        ("odx", ctypes.c_double), ("ody", ctypes.c_double), ("idx", ctypes.c_double), ("idy", ctypes.c_double),
+        ("oarea", ctypes.c_int * 4),
+        ("have_oarea", ctypes.c_int),
+        ("interpolate", ctypes.c_int),
+        ("extend", ctypes.c_int),
+        ("premultiplied", ctypes.c_int),
+        ("force_tiles", ctypes.c_int),
+        ("n_background", ctypes.c_int),
+        ("background", ctypes.c_double * 64),
+    ]
+
+
 def _load():
     # PyTorch-ROCm carries its own HIP runtime (soname libamdhip64.so).  Import it first so
     # libvipship.so, which needs that soname, binds to the SAME runtime: device pointers,
@@ -270,6 +288,16 @@ _SIGNATURES = {
     "vips_hip_morph": (c_int, [c_void_p, P(c_void_p), P(c_double), c_int, c_int, c_int]),
     "vips_hip_premultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_unpremultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
+    # affine / similarity / rotate
+    "vips_hip_affine_defaults": (None, [P(Affine)]),
+    "vips_hip_affine_plan_new": (c_void_p, [P(Affine), c_int, c_int, c_int, c_int, c_int]),
+    "vips_hip_affine_plan_free": (None, [c_void_p]),
+    "vips_hip_affine_plan_get": (c_int, [c_void_p, c_int]),
+    "vips_hip_affine_need": (None, [c_void_p, c_int, c_int, c_int, c_int, P(c_int)]),
+    "vips_hip_affine_gen": (c_int, [c_void_p, RegionP, RegionP, c_int]),
+    "vips_hip_affine": (c_int, [c_void_p, P(c_void_p), P(Affine)]),
+    "vips_hip_similarity": (c_int, [c_void_p, P(c_void_p), c_double, c_double, P(Affine)]),
+    "vips_hip_rotate": (c_int, [c_void_p, P(c_void_p), c_double, P(Affine)]),
 }
 
 MISSING = []

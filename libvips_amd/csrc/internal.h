@@ -189,4 +189,28 @@ int rank_run(const char *domain, NbArgs a, int format);
 int morph_run(const char *domain, NbArgs a, const unsigned char *mask, int dilate);
 int rank_tile(int what);
 int morph_tile(int what);
+// affine.hip: vips_affine_gen on checked regions (ops_affine.cpp checks them and fills everything).  Coordinates are
+// the reference's: ox = (double) (rect start + oarea_left) - odx, x = ia * ox + ib * oy, -= tidx (idx less the
+// one-pel embed), += window_offset, then += ia per pixel from the rect's left edge, rects starting at multiples of
+// tile_width (0: whole rows; the x of a column then comes from a table made on the host and y does not move).
+struct AffineArgs {
+	const unsigned char *in;
+	unsigned char *out;
+	long long in_stride, out_stride;          // bytes
+	int in_left, in_top, in_width, in_height; // the input window, pels of the whole image; in_width == 0: no window
+	int im_width, im_height;                  // the whole input image
+	int out_left, out_top, out_width, out_height; // `out` points at pel (out_left, out_top) of the output image
+	int bands;                                // elements a pel
+	int window_offset;
+	int extend;     // VipsHipExtend
+	int tile_width; // 0: whole rows
+	int oarea_left, oarea_top;
+	double ia, ib, ic, id, odx, ody, tidx, tidy;
+	const double *tabx; // tile_width == 0: the x of output column out_left + i
+	const void *tables; // BicubicTables, interp_device.h
+	unsigned char ink[VIPS_HIP_AFFINE_MAX_PEL];  // the pel of what lies outside the clip rectangle
+	unsigned char fill[VIPS_HIP_AFFINE_MAX_PEL]; // the pel round the image under extend black / white / background
+};
+// format: uchar .. int or float; interpolate: VipsHipInterpolate
+int affine_run(const char *domain, AffineArgs a, int format, int interpolate);
 } // namespace vh

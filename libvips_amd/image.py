@@ -65,6 +65,9 @@ ANGLE_NAMES = {v: k for k, v in ANGLES.items()}
 DIRECTIONS = {"horizontal": 0, "vertical": 1}
 # VipsOperationMorphology (include/vips/morphology.h)
 MORPHOLOGIES = {"erode": 0, "dilate": 1}
+# VipsExtend (include/vips/conversion.h); the interpolators the device has (resample/interpolate.c, bicubic.cpp)
+EXTENDS = {"black": 0, "copy": 1, "repeat": 2, "mirror": 3, "white": 4, "background": 5}
+INTERPOLATORS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
 # VipsInterpretation (include/vips/image.h:94-118)
 INTERPRETATIONS = {
     "multiband": 0,
@@ -386,6 +389,45 @@ class Image(object):
         if m.ndim == 1:
             m = m[None, :]
         return m
+
+    # vips_affine / vips_similarity / vips_rotate, with pyvips' argument names
+    @staticmethod
+    def affine_args(matrix=(1, 0, 0, 1), interpolate="bilinear", oarea=None, odx=0, ody=0, idx=0, idy=0, background=None,
+                    extend="background", premultiplied=False):
+        """The VipsHipAffine of these arguments (also what vips_hip_affine_plan_new takes)."""
+        args = _ffi.Affine()
+        lib.vips_hip_affine_defaults(ctypes.byref(args))
+        args.a, args.b, args.c, args.d = [float(v) for v in matrix]
+        if isinstance(interpolate, str) and interpolate.lower() not in INTERPOLATORS:
+            raise _ffi.VipsHipError("affine: interpolator %s is outside the HIP path (nearest, bilinear, bicubic)"
+                                    % interpolate)
+        args.interpolate = _enum(INTERPOLATORS, interpolate, "interpolate")
+        if oarea is not None:
+            if len(oarea) != 4:
+                raise _ffi.VipsHipError("affine: vector must have 4 elements")
+            args.oarea[:] = [int(v) for v in oarea]
+            args.have_oarea = 1
+        args.odx, args.ody, args.idx, args.idy = float(odx), float(ody), float(idx), float(idy)
+        if background is not None:
+            background = [float(v) for v in np.atleast_1d(background)]
+            if len(background) > _ffi.Affine.MAX_BACKGROUND:
+                raise _ffi.VipsHipError("affine: background of more than %d elements" % _ffi.Affine.MAX_BACKGROUND)
+            args.n_background = len(background)
+            args.background[:len(background)] = background
+        args.extend = _enum(EXTENDS, extend, "extend")
+        args.premultiplied = int(bool(premultiplied))
+        return args
+
+    def affine(self, matrix, **kwargs):
+        """vips_affine: ``matrix`` is (a, b, c, d); interpolate "nearest" / "bilinear" / "bicubic", ``oarea`` (left,
+        top, width, height), odx, ody, idx, idy, background, extend and premultiplied as in pyvips."""
+        return self._unary(lib.vips_hip_affine, ctypes.byref(self.affine_args(matrix, **kwargs)))
+
+    def similarity(self, scale=1.0, angle=0.0, **kwargs):
+        return self._unary(lib.vips_hip_similarity, float(scale), float(angle), ctypes.byref(self.affine_args(**kwargs)))
+
+    def rotate(self, angle, **kwargs):
+        return self._unary(lib.vips_hip_rotate, float(angle), ctypes.byref(self.affine_args(**kwargs)))
 
     def conv(self, mask, scale=1.0, offset=0.0, precision="float", layers=5, cluster=1):
         m = self._mask(mask)
