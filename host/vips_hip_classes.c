@@ -1565,6 +1565,273 @@ vips_morph_hip_init(VipsMorphHip *morph)
 	morph->morph = VIPS_OPERATION_MORPHOLOGY_ERODE;
 }
 
+/* sobel_hip / scharr_hip / prewitt_hip: convolution/edge.c:205-334.  No arguments beside in and out.  The region form
+ * (vips_hip_edge_gen) reads one row above and one below a strip. */
+typedef struct _VipsSobelHip {
+	VipsHipOp parent_instance;
+} VipsSobelHip;
+typedef VipsSobelHip VipsScharrHip;
+typedef VipsSobelHip VipsPrewittHip;
+
+static int
+edge_hip_which(VipsHipOp *op)
+{
+	const char *nick = VIPS_OBJECT_GET_CLASS(op)->nickname;
+
+	return strcmp(nick, "sobel_hip") == 0 ? VIPS_HIP_EDGE_SOBEL
+		: strcmp(nick, "scharr_hip") == 0 ? VIPS_HIP_EDGE_SCHARR
+										  : VIPS_HIP_EDGE_PREWITT;
+}
+
+static int
+vips_sobel_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	switch (edge_hip_which(op)) {
+	case VIPS_HIP_EDGE_SOBEL:
+		return vips_hip_sobel(in, out);
+	case VIPS_HIP_EDGE_SCHARR:
+		return vips_hip_scharr(in, out);
+	default:
+		return vips_hip_prewitt(in, out);
+	}
+}
+
+static void
+vips_sobel_hip_strip_close(VipsHipOp *op, void *plan)
+{
+}
+
+static int
+vips_sobel_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	*plan = op; /* (the class is the plan) */
+
+	return 0;
+}
+
+static void
+vips_sobel_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	vips_hip_edge_need(out_top, out_rows, in_top, in_rows);
+}
+
+static int
+vips_sobel_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_edge_gen(in, out, edge_hip_which(op));
+}
+
+#define vips_scharr_hip_compute vips_sobel_hip_compute
+#define vips_prewitt_hip_compute vips_sobel_hip_compute
+
+HIP_SUBCLASS_FULL(VipsSobelHip, vips_sobel_hip, "sobel_hip", "Sobel edge detector (MI355X)", HIP_STRIPS(vips_sobel_hip))
+HIP_SUBCLASS_FULL(VipsScharrHip, vips_scharr_hip, "scharr_hip", "Scharr edge detector (MI355X)", HIP_STRIPS(vips_sobel_hip))
+HIP_SUBCLASS_FULL(VipsPrewittHip, vips_prewitt_hip, "prewitt_hip", "Prewitt edge detector (MI355X)",
+	HIP_STRIPS(vips_sobel_hip))
+
+static void
+vips_sobel_hip_args(VipsSobelHipClass *class)
+{
+}
+
+static void
+vips_scharr_hip_args(VipsScharrHipClass *class)
+{
+}
+
+static void
+vips_prewitt_hip_args(VipsPrewittHipClass *class)
+{
+}
+
+static void
+vips_sobel_hip_init(VipsSobelHip *edge)
+{
+}
+
+static void
+vips_scharr_hip_init(VipsScharrHip *edge)
+{
+}
+
+static void
+vips_prewitt_hip_init(VipsPrewittHip *edge)
+{
+}
+
+/* compass_hip: convolution/compass.c:149-214.  The original's build has run vips_rot45 on the mask by then (an even or
+ * non-square mask fails there, in its words).  The plan of the C ABI is the strip plan; a strip reads half the mask
+ * above and the rest below. */
+typedef struct _VipsCompassHip {
+	VipsHipOp parent_instance;
+	VipsImage *mask;
+	int times;
+	VipsAngle45 angle;
+	VipsCombine combine;
+	VipsPrecision precision;
+	int layers;
+	int cluster;
+} VipsCompassHip;
+
+typedef struct _CompassStrip {
+	VipsHipCompass *plan;
+	int size;
+} CompassStrip;
+
+static VipsHipCompass *
+compass_hip_plan(VipsCompassHip *compass, int *size)
+{
+	VipsImage *M;
+	VipsHipCompass *plan;
+
+	if (vips_check_matrix("compass_hip", compass->mask, &M))
+		return NULL;
+	plan = vips_hip_compass_new(VIPS_MATRIX(M, 0, 0), M->Xsize, M->Ysize, vips_image_get_scale(M), vips_image_get_offset(M),
+		compass->times, compass->angle, compass->combine, compass->precision, compass->layers, compass->cluster);
+	if (size)
+		*size = M->Ysize;
+	g_object_unref(M);
+
+	return plan;
+}
+
+static int
+vips_compass_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsCompassHip *compass = (VipsCompassHip *) op;
+	VipsImage *M;
+	int result;
+
+	if (vips_check_matrix("compass_hip", compass->mask, &M))
+		return -1;
+	result = vips_hip_compass(in, out, VIPS_MATRIX(M, 0, 0), M->Xsize, M->Ysize, vips_image_get_scale(M),
+		vips_image_get_offset(M), compass->times, compass->angle, compass->combine, compass->precision, compass->layers,
+		compass->cluster);
+	g_object_unref(M);
+
+	return result;
+}
+
+static void
+vips_compass_hip_strip_close(VipsHipOp *op, void *plan)
+{
+	CompassStrip *p = (CompassStrip *) plan;
+
+	if (p) {
+		vips_hip_compass_free(p->plan);
+		g_free(p);
+	}
+}
+
+static int
+vips_compass_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	CompassStrip *p = g_new0(CompassStrip, 1);
+
+	if (!(p->plan = compass_hip_plan((VipsCompassHip *) op, &p->size))) {
+		g_free(p);
+		return hip_fail("compass_hip");
+	}
+	*plan = p;
+
+	return 0;
+}
+
+static void
+vips_compass_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	vips_hip_rank_need(((CompassStrip *) plan)->size, out_top, out_rows, in_top, in_rows);
+}
+
+static int
+vips_compass_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_compass_gen(((CompassStrip *) plan)->plan, in, out);
+}
+
+HIP_SUBCLASS_FULL(VipsCompassHip, vips_compass_hip, "compass_hip", "convolve with rotating mask (MI355X)",
+	HIP_STRIPS(vips_compass_hip))
+
+static void
+vips_compass_hip_args(VipsCompassHipClass *class)
+{
+	VIPS_ARG_IMAGE(class, "mask", 20, "Mask", "Input matrix image",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCompassHip, mask));
+	VIPS_ARG_INT(class, "times", 101, "Times", "Rotate and convolve this many times",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCompassHip, times), 1, 1000, 2);
+	VIPS_ARG_ENUM(class, "angle", 103, "Angle", "Rotate mask by this much between convolutions",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCompassHip, angle), VIPS_TYPE_ANGLE45, VIPS_ANGLE45_D90);
+	VIPS_ARG_ENUM(class, "combine", 104, "Combine", "Combine convolution results like this",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCompassHip, combine), VIPS_TYPE_COMBINE, VIPS_COMBINE_MAX);
+	VIPS_ARG_ENUM(class, "precision", 203, "Precision", "Convolve with this precision",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCompassHip, precision), VIPS_TYPE_PRECISION, VIPS_PRECISION_FLOAT);
+	VIPS_ARG_INT(class, "layers", 204, "Layers", "Use this many layers in approximation",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCompassHip, layers), 1, 1000, 5);
+	VIPS_ARG_INT(class, "cluster", 205, "Cluster", "Cluster lines closer than this in approximation",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCompassHip, cluster), 1, 100, 1);
+}
+
+static void
+vips_compass_hip_init(VipsCompassHip *compass)
+{
+	compass->times = 2;
+	compass->angle = VIPS_ANGLE45_D90;
+	compass->combine = VIPS_COMBINE_MAX;
+	compass->precision = VIPS_PRECISION_FLOAT;
+	compass->layers = 5;
+	compass->cluster = 1;
+}
+
+/* canny_hip: convolution/canny.c:431-479.  Whole images by vips_hip_canny; above the HBM budget in row strips with a
+ * halo: the blur's radius and, for the gradient and the thinning behind it, two rows above and one below, so that what
+ * a strip's own edges disturb is cut away. */
+typedef struct _VipsCannyHip {
+	VipsHipOp parent_instance;
+	double sigma;
+	VipsPrecision precision;
+} VipsCannyHip;
+
+static int
+vips_canny_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsCannyHip *canny = (VipsCannyHip *) op;
+
+	return vips_hip_canny(in, out, canny->sigma, canny->precision);
+}
+
+static int
+vips_canny_hip_halo(VipsHipOp *op, VipsImage *in, int *above, int *below)
+{
+	VipsCannyHip *canny = (VipsCannyHip *) op;
+	int n = 1;
+
+	if (canny->sigma >= 0.2 && /* (gaussblur.c:82: below that the blur is a copy) */
+		(n = vips_hip_gaussmat(canny->sigma, 0.2, 1, canny->precision, NULL, 0, NULL)) < 1)
+		return hip_fail("canny_hip");
+	*above = n / 2 + 2;
+	*below = n - 1 - n / 2 + 1;
+
+	return 0;
+}
+
+HIP_SUBCLASS_FULL(VipsCannyHip, vips_canny_hip, "canny_hip", "Canny edge detector (MI355X)", HIP_HALO(vips_canny_hip))
+
+static void
+vips_canny_hip_args(VipsCannyHipClass *class)
+{
+	VIPS_ARG_DOUBLE(class, "sigma", 10, "Sigma", "Sigma of Gaussian",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCannyHip, sigma), 0.01, 1000, 1.4);
+	VIPS_ARG_ENUM(class, "precision", 103, "Precision", "Convolve with this precision",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCannyHip, precision), VIPS_TYPE_PRECISION, VIPS_PRECISION_FLOAT);
+}
+
+static void
+vips_canny_hip_init(VipsCannyHip *canny)
+{
+	canny->sigma = 1.4;
+	canny->precision = VIPS_PRECISION_FLOAT;
+}
+
 /* affine_hip / similarity_hip / rotate_hip: resample/affine.c:627-718, similarity.c:113-300.  One instance struct for
  * the three (similarity and rotate make their matrix, similarity.c:89-92).  The original operation's build has checked
  * the arguments by then and gives the header; the plan of the C ABI (vips_hip_affine_plan_new) restates it without

@@ -1549,6 +1549,7 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *     (entropy, attention: conversion/smartcrop.c);
  *   - rot / flip / autorot of an image over the HBM budget (they have no strip form);
  *   - rank of double images (the device kernels sort keys of at most 32 bits);
+ *   - sobel / scharr / prewitt / compass / canny of double images, canny of pels wider than its kernel's tile holds;
  *   - affine / similarity / rotate of double images, with an interpolator other than nearest, bilinear and bicubic
  *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands.
  */
@@ -1568,6 +1569,13 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 		2 * (guint64) VIPS_IMAGE_SIZEOF_IMAGE(in) > hip_budget())
 		return TRUE;
 	if (strcmp(nick, "rank_hip") == 0 && in->BandFmt == VIPS_FORMAT_DOUBLE)
+		return TRUE;
+	/* the edge detectors refuse double images by name; canny's kernel takes pels of up to vips_hip_edge_step(5) bands */
+	if ((strcmp(nick, "sobel_hip") == 0 || strcmp(nick, "scharr_hip") == 0 || strcmp(nick, "prewitt_hip") == 0 ||
+			strcmp(nick, "compass_hip") == 0 || strcmp(nick, "canny_hip") == 0) &&
+		in->BandFmt == VIPS_FORMAT_DOUBLE)
+		return TRUE;
+	if (strcmp(nick, "canny_hip") == 0 && in->Bands > vips_hip_edge_step(5))
 		return TRUE;
 	if (strcmp(nick, "affine_hip") == 0 || strcmp(nick, "similarity_hip") == 0 || strcmp(nick, "rotate_hip") == 0) {
 		VipsInterpolate *interpolate = NULL;
@@ -1717,7 +1725,7 @@ vips_hip_op_init(VipsHipOp *op)
 
 /* ------------------------------------------------------------------ subclasses */
 
-/* (the 25 operation classes: arguments, defaults, hooks) */
+/* (the 30 operation classes: arguments, defaults, hooks) */
 #include "vips_hip_classes.c"
 
 /* ------------------------------------------------------------------ registration */
@@ -1750,6 +1758,11 @@ g_module_check_init(GModule *module)
 	vips_unpremultiply_hip_get_type();
 	vips_rank_hip_get_type();
 	vips_morph_hip_get_type();
+	vips_sobel_hip_get_type();
+	vips_scharr_hip_get_type();
+	vips_prewitt_hip_get_type();
+	vips_compass_hip_get_type();
+	vips_canny_hip_get_type();
 	vips_affine_hip_get_type();
 	vips_similarity_hip_get_type();
 	vips_rotate_hip_get_type();

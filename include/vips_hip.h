@@ -507,6 +507,97 @@ VIPS_HIP_API int vips_hip_morph_gen(const VipsHipRegion *in, const VipsHipRegion
 VIPS_HIP_API void vips_hip_rank_need(int window_height, int top, int height, int *in_top, int *in_height);
 VIPS_HIP_API int vips_hip_rank_step(int what);
 
+/* ---------------------------------------------------------- edge detectors
+ *
+ * vips_sobel, vips_scharr and vips_prewitt (convolution/edge.c): a fixed 3 x 3 mask and its rot90 over the image,
+ * the two results combined per element; any band count, the output is uchar.
+ *   uchar input   vips_edge_build_uchar (edge.c:112-153): two integer convolutions with scale 2 and offset 128, each
+ *                 rounded and clipped to 0 .. 255 as vips_convi_gen stores it, then |2 (c1 - 128)| + |2 (c2 - 128)|
+ *                 saturated at 255 -- ONE kernel, one read of the image and one write (gate edge_u8).
+ *   other input   vips_edge_build_float (:157-183): two float convolutions (each mask run as its own mask through the
+ *                 kernels of vips_hip_conv_gen), then x * x + y * y in float, the square root in double, vips_cast to
+ *                 uchar (gate edge_combine_f32).  char ... int and float; double and complex images are refused by
+ *                 name.
+ * (uchar images with the Highway arithmetic of convi selected, vips_hip_vector_set_enabled(), and pels too wide for
+ * the fused kernel's tile take two vips_hip_conv_gen passes and the gate edge_combine_u8: the same pixels.)
+ * The input window must hold the out rect grown by one pel all round, clipped to the image: rows
+ * vips_hip_edge_need() names.  vips_hip_edge_step: 0 / 1 the elements of a row / the rows a block of the fused kernel
+ * makes, 2 the widest pel (bands) it takes (3 .. 5: the same for vips_hip_canny_gen's kernel, below).
+ */
+typedef enum {
+	VIPS_HIP_EDGE_SOBEL = 0,
+	VIPS_HIP_EDGE_SCHARR,
+	VIPS_HIP_EDGE_PREWITT,
+	VIPS_HIP_EDGE_LAST
+} VipsHipEdge;
+VIPS_HIP_API int vips_hip_edge_gen(const VipsHipRegion *in, const VipsHipRegion *out, int edge);
+VIPS_HIP_API void vips_hip_edge_need(int top, int height, int *in_top, int *in_height);
+VIPS_HIP_API int vips_hip_edge_step(int what);
+
+/* vips_compass (convolution/compass.c): the image convolved with the mask `times` times, the mask turned by `angle`
+ * (vips_rot45) between convolutions, the absolute values combined by max, min or sum.  The plan restates
+ * vips_compass_build on the host: rot45 of an odd square matrix is pure index movement with period 8, so `times`
+ * convolutions are at most eight distinct ones, each with a multiplicity (which only a sum sees).  A mask that is not
+ * odd and square gives vips_rot45's error, "rot45: images must be odd and square".
+ *   uchar, precision integer, a 3 x 3 mask   ONE kernel: every distinct mask's integer convolution, rounded, offset
+ *                 and clipped as vips_convi_gen stores it, then max / min (uchar out) or the sum (uint out) -- one
+ *                 read of the image, one write (gate compass_u8).
+ *   everything else   every distinct mask through vips_hip_conv_gen / vips_hip_conva_gen as its own mask, then one
+ *                 kernel for vips_abs and the combine over their results (gate compass_combine).  A float sum adds
+ *                 its `times` terms in the reference's order.
+ * The output format is what the reference's vips_bandrank / vips_sum make of the convolutions' format:
+ * vips_hip_compass_out_format.  double and complex images are refused by name.  The input window must hold the out
+ * rect grown by the mask (origin size / 2), clipped to the image: vips_hip_rank_need(size, ...) names its rows.
+ */
+typedef enum { /* VipsAngle45: steps of 45 degrees */
+	VIPS_HIP_ANGLE45_D0 = 0,
+	VIPS_HIP_ANGLE45_D45,
+	VIPS_HIP_ANGLE45_D90,
+	VIPS_HIP_ANGLE45_D135,
+	VIPS_HIP_ANGLE45_D180,
+	VIPS_HIP_ANGLE45_D225,
+	VIPS_HIP_ANGLE45_D270,
+	VIPS_HIP_ANGLE45_D315
+} VipsHipAngle45;
+typedef enum { /* VipsCombine */
+	VIPS_HIP_COMBINE_MAX = 0,
+	VIPS_HIP_COMBINE_SUM = 1,
+	VIPS_HIP_COMBINE_MIN = 2
+} VipsHipCombine;
+typedef struct _VipsHipCompass VipsHipCompass;
+/* vips_rot45 of a width x height matrix of doubles (host only, no device needed). */
+VIPS_HIP_API int vips_hip_rot45(const double *in, int width, int height, int angle, double *out);
+VIPS_HIP_API VipsHipCompass *vips_hip_compass_new(const double *mask, int mask_width, int mask_height, double scale,
+	double offset, int times, int angle, int combine, int precision, int layers, int cluster);
+VIPS_HIP_API void vips_hip_compass_free(VipsHipCompass *plan);
+/* The distinct masks (each mask_width x mask_height doubles, the k-th one the mask turned k times) and how many of
+ * the `times` convolutions run each; at most @max of them are written.  Returns their number (host only). */
+VIPS_HIP_API int vips_hip_compass_get_masks(const VipsHipCompass *plan, double *masks, int *mult, int max);
+VIPS_HIP_API int vips_hip_compass_out_format(const VipsHipCompass *plan, int format);
+VIPS_HIP_API int vips_hip_compass_gen(const VipsHipCompass *plan, const VipsHipRegion *in, const VipsHipRegion *out);
+
+/* vips_canny (convolution/canny.c) behind its blur: vips_canny_gradient (the 2 x 2 mask -1 1 / -1 1 and its rot90,
+ * origin at (1, 1)), vips_canny_polar, the one-pel vips_embed(COPY) of the polar image and vips_canny_thin in ONE
+ * kernel on a window of the BLURRED image (vips_hip_gaussblur makes it); any band count up to vips_hip_edge_step(5).
+ *   a uchar blur (uchar input with precision integer or approximate)   integer gradients with offset 128 and their
+ *                 clip, the 256-entry atan2 table (vips_hip_canny_table: vips_atan2_init's own expression on the
+ *                 host), integer thinning; uchar out (gate canny_polar_thin_u8).
+ *   any other blur (the default precision, float, turns every input into one)   float gradients as convf sums them,
+ *                 POLAR(float) in double rounded to float, THIN(float) in float with every operation rounded; float
+ *                 out (gate canny_polar_thin_f32).  double and complex images are refused by name.
+ * Bit-identical to the reference but for one spot: theta is atan2 in double and the device's atan2 is not the host
+ * library's; both are within a couple of ulp of the true value, so the floats can differ only where the double lies
+ * within a few ulp of a float rounding boundary.  The float kernel COUNTS the pels whose theta would round to another
+ * float had atan2's result been 4 ulp off either way: vips_hip_canny_marginal() returns that count for the calling
+ * thread's device since it was last read (and clears it).  Zero means bit-identical.
+ * The window must hold the out rect grown by two pels above and to the left and one below and to the right, clipped
+ * to the image: rows vips_hip_canny_need() names.  vips_hip_edge_step 3 / 4: the pels / rows a block makes.
+ */
+VIPS_HIP_API void vips_hip_canny_table(unsigned char *table);
+VIPS_HIP_API void vips_hip_canny_need(int top, int height, int *in_top, int *in_height);
+VIPS_HIP_API int vips_hip_canny_gen(const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API long long vips_hip_canny_marginal(void);
+
 /* vips_sharpen_generate (convolution/sharpen.c:116-168): LabS in, LabS out; the
  * blurred L band comes from a vips_hip_conv_gen pass the caller ran.
  */
@@ -704,6 +795,18 @@ VIPS_HIP_API int vips_hip_rank(VipsHipImage *in, VipsHipImage **out, int width, 
 VIPS_HIP_API int vips_hip_median(VipsHipImage *in, VipsHipImage **out, int size);
 VIPS_HIP_API int vips_hip_morph(VipsHipImage *in, VipsHipImage **out,
 	const double *mask, int mask_width, int mask_height, int morph);
+/* vips_sobel, vips_scharr, vips_prewitt (convolution/edge.c) on whole images: see vips_hip_edge_gen above.  The
+ * result has the size and bands of the input and is uchar. */
+VIPS_HIP_API int vips_hip_sobel(VipsHipImage *in, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_scharr(VipsHipImage *in, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_prewitt(VipsHipImage *in, VipsHipImage **out);
+/* vips_canny (canny.c:380-429): vips_hip_gaussblur(sigma, precision), then vips_hip_canny_gen on the blurred image.
+ * The class defaults: sigma 1.4, precision float. */
+VIPS_HIP_API int vips_hip_canny(VipsHipImage *in, VipsHipImage **out, double sigma, int precision);
+/* vips_compass on a whole image: see vips_hip_compass_gen above (the class defaults: times 2, angle d90, combine max,
+ * precision float, layers 5, cluster 1). */
+VIPS_HIP_API int vips_hip_compass(VipsHipImage *in, VipsHipImage **out, const double *mask, int mask_width, int mask_height,
+	double scale, double offset, int times, int angle, int combine, int precision, int layers, int cluster);
 VIPS_HIP_API int vips_hip_conv(VipsHipImage *in, VipsHipImage **out,
 	const double *mask, int mask_width, int mask_height, double scale, double offset,
 	int precision);

@@ -42,3 +42,14 @@ def gate_report():
         name, n, ms = line.rsplit(" ", 2)
         out[name] = (int(n), float(ms))
     return out
+
+
+def canny_marginal():
+    """vips_hip_canny_marginal: the pels of the float canny kernel, since the last call, whose theta sat within 4 ulp
+    (of atan2's result) of a float rounding boundary; reading clears the count.  Zero: bit-identical to libvips."""
+    n = lib.vips_hip_canny_marginal()
+    if n < 0:
+        from ._ffi import _raise
+
+        _raise("canny_marginal")
+    return n

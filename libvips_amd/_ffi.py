@@ -286,6 +286,29 @@ _SIGNATURES = {
     "vips_hip_rank": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int]),
     "vips_hip_median": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_morph": (c_int, [c_void_p, P(c_void_p), P(c_double), c_int, c_int, c_int]),
+    # sobel / scharr / prewitt
+    "vips_hip_edge_gen": (c_int, [RegionP, RegionP, c_int]),
+    "vips_hip_edge_need": (None, [c_int, c_int, P(c_int), P(c_int)]),
+    "vips_hip_edge_step": (c_int, [c_int]),
+    "vips_hip_sobel": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_scharr": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_prewitt": (c_int, [c_void_p, P(c_void_p)]),
+    # canny
+    "vips_hip_canny_table": (None, [P(ctypes.c_ubyte)]),
+    "vips_hip_canny_need": (None, [c_int, c_int, P(c_int), P(c_int)]),
+    "vips_hip_canny_gen": (c_int, [RegionP, RegionP]),
+    "vips_hip_canny_marginal": (ctypes.c_longlong, []),
+    "vips_hip_canny": (c_int, [c_void_p, P(c_void_p), c_double, c_int]),
+    # compass
+    "vips_hip_rot45": (c_int, [P(c_double), c_int, c_int, c_int, P(c_double)]),
+    "vips_hip_compass_new": (c_void_p, [P(c_double), c_int, c_int, c_double, c_double, c_int, c_int, c_int, c_int, c_int,
+                                        c_int]),
+    "vips_hip_compass_free": (None, [c_void_p]),
+    "vips_hip_compass_get_masks": (c_int, [c_void_p, P(c_double), P(c_int), c_int]),
+    "vips_hip_compass_out_format": (c_int, [c_void_p, c_int]),
+    "vips_hip_compass_gen": (c_int, [c_void_p, RegionP, RegionP]),
+    "vips_hip_compass": (c_int, [c_void_p, P(c_void_p), P(c_double), c_int, c_int, c_double, c_double, c_int, c_int, c_int,
+                                 c_int, c_int, c_int]),
     "vips_hip_premultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_unpremultiply": (c_int, [c_void_p, P(c_void_p), c_int]),
     # affine / similarity / rotate

@@ -189,6 +189,42 @@ int rank_run(const char *domain, NbArgs a, int format);
 int morph_run(const char *domain, NbArgs a, const unsigned char *mask, int dilate);
 int rank_tile(int what);
 int morph_tile(int what);
+// ops_morphology.cpp: the checks every neighbourhood gen makes on its pair of regions, and the geometry of the launch:
+// @in must hold the out rect grown by the window (origin win_w / 2, win_h / 2) and clipped to the image.
+int nb_geometry(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out, int win_w, int win_h, NbArgs *a);
+// edge.hip: the fused uchar kernel of vips_sobel and its siblings on checked regions (ops_edge.cpp), `mask` and
+// `mask90` 3 x 3 in raster order; edge_u8_fits: the tile of so wide a pel fits the kernel's LDS; edge_tile as above
+// (2: the widest pel that fits).  edge_combine_run: the general tier's tail on the two convolutions' rows.
+int edge_u8_run(const char *domain, NbArgs a, const int *mask, const int *mask90);
+int edge_u8_fits(int bands);
+int edge_tile(int what);
+int edge_combine_run(const char *domain, const void *c1, long long c1_stride, const void *c2, long long c2_stride, void *out,
+	long long out_stride, long long elems, int height, int is_float);
+// ... of vips_compass for uchar, precision integer, 3 x 3: `masks` n x 9 ints, `mult` how often each runs, `combine` a
+// VipsHipCombine; compass_u8_takes: the kernel takes these masks.  compass_combine_run: the general tier's tail on n
+// planes of convolutions in `format`.
+int compass_u8_takes(int bands, const int *masks, int n, int scale);
+int compass_u8_run(const char *domain, NbArgs a, const int *masks, const int *mult, int n, int scale, int offset, int combine);
+int compass_combine_run(const char *domain, const void *in, long long in_stride, long long plane, int n, int times, int format,
+	int combine, void *out, long long out_stride, long long elems, int height);
+// ... of vips_canny behind its blur: the gradient pair, the polar image and the thinning on a checked window of the
+// blurred image (ops_edge.cpp checks it and fills everything but the table).  canny_tile: 0 / 1 the pels / rows a block
+// makes, 2 the widest pel.
+constexpr int CANNY_TABLE = 256; // bytes: the atan2 table of the uchar path
+struct CannyArgs {
+	const unsigned char *in; // the blurred image's window
+	unsigned char *out;
+	long long in_stride, out_stride;          // bytes
+	int in_left, in_top, in_width, in_height; // the window, pels of the whole image
+	int im_width, im_height;
+	int out_left, out_top, out_width, out_height; // `out` points at pel (out_left, out_top)
+	int bands;
+	int format;             // of the blurred image: uchar takes the integer kernel, everything else the float one
+	unsigned int *marginal; // float kernel: the counter behind vips_hip_canny_marginal
+	unsigned int atan2_table[CANNY_TABLE / 4]; // vips_canny_polar_atan2 (uchar kernel)
+};
+int canny_run(const char *domain, CannyArgs a, const unsigned char *table);
+int canny_tile(int what);
 // affine.hip: vips_affine_gen on checked regions (ops_affine.cpp checks them and fills everything).  Coordinates are
 // the reference's: ox = (double) (rect start + oarea_left) - odx, x = ia * ox + ib * oy, -= tidx (idx less the
 // one-pel embed), += window_offset, then += ia per pixel from the rect's left edge, rects starting at multiples of

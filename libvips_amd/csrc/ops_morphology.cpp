@@ -34,9 +34,11 @@ struct DeviceBlock {
 	~DeviceBlock() { vips_hip_free(p); }
 };
 
+} // namespace
+
 // The checks every neighbourhood gen makes on its pair of regions, and the geometry of the launch: @in must hold the
 // out rect grown by the window (origin win_w / 2, win_h / 2) and clipped to the image.
-int nb_geometry(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out, int win_w, int win_h, NbArgs *a)
+int vh::nb_geometry(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out, int win_w, int win_h, NbArgs *a)
 {
 	if (in->bands != out->bands) {
 		error(domain, "output region has the wrong bands");
@@ -90,8 +92,6 @@ int nb_geometry(const char *domain, const VipsHipRegion *in, const VipsHipRegion
 	a->key_xor = 0;
 	return 0;
 }
-
-} // namespace
 
 extern "C" {
 

@@ -65,6 +65,8 @@ ANGLE_NAMES = {v: k for k, v in ANGLES.items()}
 DIRECTIONS = {"horizontal": 0, "vertical": 1}
 # VipsOperationMorphology (include/vips/morphology.h)
 MORPHOLOGIES = {"erode": 0, "dilate": 1}
+ANGLES45 = {"d0": 0, "d45": 1, "d90": 2, "d135": 3, "d180": 4, "d225": 5, "d270": 6, "d315": 7}
+COMBINES = {"max": 0, "sum": 1, "min": 2}
 # VipsExtend (include/vips/conversion.h); the interpolators the device has (resample/interpolate.c, bicubic.cpp)
 EXTENDS = {"black": 0, "copy": 1, "repeat": 2, "mirror": 3, "white": 4, "background": 5}
 INTERPOLATORS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
@@ -382,6 +384,32 @@ class Image(object):
         m = self._mask(mask)
         return self._unary(lib.vips_hip_morph, m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), m.shape[1], m.shape[0],
                            _enum(MORPHOLOGIES, morph, "morph"))
+
+    # vips_sobel / vips_scharr / vips_prewitt: the result is uchar
+    def sobel(self):
+        return self._unary(lib.vips_hip_sobel)
+
+    def scharr(self):
+        return self._unary(lib.vips_hip_scharr)
+
+    def prewitt(self):
+        return self._unary(lib.vips_hip_prewitt)
+
+    def canny(self, sigma=1.4, precision="float"):
+        """vips_canny: blur, gradient, polar image and thinning.  uchar for a uchar image with precision integer or
+        approximate, else float.  ``libvips_amd.canny_marginal()`` says how many pels of the float path sat too close
+        to a rounding boundary of theta to be sure of."""
+        return self._unary(lib.vips_hip_canny, float(sigma), _enum(PRECISIONS, precision, "precision"))
+
+    def compass(self, mask, times=2, angle="d90", combine="max", precision="float", layers=5, cluster=1, scale=1.0,
+                offset=0.0):
+        """vips_compass: convolve ``times`` times, the (odd, square) mask turned by ``angle`` in between, and combine
+        the absolute values.  max and min keep the convolution's format, sum widens it as vips_sum does."""
+        m = self._mask(mask)
+        return self._unary(lib.vips_hip_compass, m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), m.shape[1], m.shape[0],
+                           float(scale), float(offset), int(times), _enum(ANGLES45, angle, "angle"),
+                           _enum(COMBINES, combine, "combine"), _enum(PRECISIONS, precision, "precision"), int(layers),
+                           int(cluster))
 
     @staticmethod
     def _mask(mask):
