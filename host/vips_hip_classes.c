@@ -1493,6 +1493,145 @@ vips_rank_hip_init(VipsRankHip *rank)
 	rank->index = 50;
 }
 
+/* hist_local_hip / stdif_hip: histogram/hist_local.c:335-383, stdif.c:322-395.  As rank_hip: a region form in the C ABI
+ * (vips_hip_hist_local_gen, vips_hip_stdif_gen: the mirror and the edge copy are by whole-image coordinates), so an
+ * image over the HBM budget goes through in row strips that read the rows vips_hip_rank_need names.  "window too
+ * large" and "image must be VIPS_FORMAT_UCHAR" are the original's build's, in its own words (hip_twin_header).  (hist_equal has no
+ * class here: vips_hist_find works its pixels out in build(), and a build of this module moves no pixels; maplut
+ * takes two images and these classes take one.) */
+typedef struct _VipsHistLocalHip {
+	VipsHipOp parent_instance;
+	int width, height, max_slope;
+} VipsHistLocalHip;
+
+static int
+vips_hist_local_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsHistLocalHip *local = (VipsHistLocalHip *) op;
+
+	return vips_hip_hist_local(in, out, local->width, local->height, local->max_slope);
+}
+
+static void
+vips_hist_local_hip_strip_close(VipsHipOp *op, void *plan)
+{
+}
+
+static int
+vips_hist_local_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	*plan = op; /* (the arguments are the plan) */
+
+	return 0;
+}
+
+static void
+vips_hist_local_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	vips_hip_rank_need(((VipsHistLocalHip *) op)->height, out_top, out_rows, in_top, in_rows);
+}
+
+static int
+vips_hist_local_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsHistLocalHip *local = (VipsHistLocalHip *) op;
+
+	return vips_hip_hist_local_gen(in, out, local->width, local->height, local->max_slope);
+}
+
+HIP_SUBCLASS_FULL(VipsHistLocalHip, vips_hist_local_hip, "hist_local_hip", "local histogram equalisation (MI355X)",
+	HIP_STRIPS(vips_hist_local_hip))
+
+static void
+vips_hist_local_hip_args(VipsHistLocalHipClass *class)
+{
+	VIPS_ARG_INT(class, "width", 4, "Width", "Window width in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsHistLocalHip, width), 1, VIPS_MAX_COORD, 1);
+	VIPS_ARG_INT(class, "height", 5, "Height", "Window height in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsHistLocalHip, height), 1, VIPS_MAX_COORD, 1);
+	VIPS_ARG_INT(class, "max_slope", 6, "Max slope", "Maximum slope (CLAHE)",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsHistLocalHip, max_slope), 0, 100, 0);
+}
+
+static void
+vips_hist_local_hip_init(VipsHistLocalHip *local)
+{
+	local->width = 1;
+	local->height = 1;
+}
+
+typedef struct _VipsStdifHip {
+	VipsHipOp parent_instance;
+	int width, height;
+	double a, m0, b, s0;
+} VipsStdifHip;
+
+static int
+vips_stdif_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsStdifHip *stdif = (VipsStdifHip *) op;
+
+	return vips_hip_stdif(in, out, stdif->width, stdif->height, stdif->a, stdif->m0, stdif->b, stdif->s0);
+}
+
+static void
+vips_stdif_hip_strip_close(VipsHipOp *op, void *plan)
+{
+}
+
+static int
+vips_stdif_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	*plan = op; /* (the arguments are the plan) */
+
+	return 0;
+}
+
+static void
+vips_stdif_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	vips_hip_rank_need(((VipsStdifHip *) op)->height, out_top, out_rows, in_top, in_rows);
+}
+
+static int
+vips_stdif_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsStdifHip *stdif = (VipsStdifHip *) op;
+
+	return vips_hip_stdif_gen(in, out, stdif->width, stdif->height, stdif->a, stdif->m0, stdif->b, stdif->s0);
+}
+
+HIP_SUBCLASS_FULL(VipsStdifHip, vips_stdif_hip, "stdif_hip", "statistical difference (MI355X)", HIP_STRIPS(vips_stdif_hip))
+
+static void
+vips_stdif_hip_args(VipsStdifHipClass *class)
+{
+	/* (stdif.c:341-395: width and height default to 11 and stop at 256) */
+	VIPS_ARG_INT(class, "width", 4, "Width", "Window width in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsStdifHip, width), 1, 256, 11);
+	VIPS_ARG_INT(class, "height", 5, "Height", "Window height in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsStdifHip, height), 1, 256, 11);
+	VIPS_ARG_DOUBLE(class, "a", 2, "Mean weight", "Weight of new mean",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsStdifHip, a), 0.0, 1.0, 0.5);
+	VIPS_ARG_DOUBLE(class, "m0", 2, "Mean", "New mean",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsStdifHip, m0), -INFINITY, INFINITY, 128.0);
+	VIPS_ARG_DOUBLE(class, "b", 2, "Deviation weight", "Weight of new deviation",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsStdifHip, b), 0.0, 2.0, 0.5);
+	VIPS_ARG_DOUBLE(class, "s0", 2, "Deviation", "New deviation",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsStdifHip, s0), -INFINITY, INFINITY, 50.0);
+}
+
+static void
+vips_stdif_hip_init(VipsStdifHip *stdif)
+{
+	stdif->width = 11;
+	stdif->height = 11;
+	stdif->a = 0.5;
+	stdif->m0 = 128.0;
+	stdif->b = 0.5;
+	stdif->s0 = 50.0;
+}
+
 typedef struct _VipsMorphHip {
 	VipsHipOp parent_instance;
 	VipsImage *mask;

@@ -1549,6 +1549,9 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *     (entropy, attention: conversion/smartcrop.c);
  *   - rot / flip / autorot of an image over the HBM budget (they have no strip form);
  *   - rank of double images (the device kernels sort keys of at most 32 bits);
+ *   - hist_local with a window of more than 65535 pels, more than 256 a side or an image of more than 16 bands (the
+ *     sliding kernel's 16-bit bins and its lanes), stdif with a window of more than 66051 pels (where the original's
+ *     own sums wrap);
  *   - sobel / scharr / prewitt / compass / canny of double images, canny of pels wider than its kernel's tile holds;
  *   - affine / similarity / rotate of double images, with an interpolator other than nearest, bilinear and bicubic
  *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands.
@@ -1570,6 +1573,18 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 		return TRUE;
 	if (strcmp(nick, "rank_hip") == 0 && in->BandFmt == VIPS_FORMAT_DOUBLE)
 		return TRUE;
+	if (strcmp(nick, "hist_local_hip") == 0 || strcmp(nick, "stdif_hip") == 0) {
+		int width = 1, height = 1;
+
+		g_object_get(op, "width", &width, "height", &height, NULL);
+		if (strcmp(nick, "stdif_hip") == 0) {
+			if ((gint64) width * height > vips_hip_stdif_step(2))
+				return TRUE;
+		}
+		else if ((gint64) width * height > 65535 || width > vips_hip_hist_local_step(2) ||
+			height > vips_hip_hist_local_step(2) || in->Bands > vips_hip_hist_local_step(3))
+			return TRUE;
+	}
 	/* the edge detectors refuse double images by name; canny's kernel takes pels of up to vips_hip_edge_step(5) bands */
 	if ((strcmp(nick, "sobel_hip") == 0 || strcmp(nick, "scharr_hip") == 0 || strcmp(nick, "prewitt_hip") == 0 ||
 			strcmp(nick, "compass_hip") == 0 || strcmp(nick, "canny_hip") == 0) &&
@@ -1725,7 +1740,7 @@ vips_hip_op_init(VipsHipOp *op)
 
 /* ------------------------------------------------------------------ subclasses */
 
-/* (the 30 operation classes: arguments, defaults, hooks) */
+/* (the 32 operation classes: arguments, defaults, hooks) */
 #include "vips_hip_classes.c"
 
 /* ------------------------------------------------------------------ registration */
@@ -1758,6 +1773,8 @@ g_module_check_init(GModule *module)
 	vips_unpremultiply_hip_get_type();
 	vips_rank_hip_get_type();
 	vips_morph_hip_get_type();
+	vips_hist_local_hip_get_type();
+	vips_stdif_hip_get_type();
 	vips_sobel_hip_get_type();
 	vips_scharr_hip_get_type();
 	vips_prewitt_hip_get_type();

@@ -507,6 +507,44 @@ VIPS_HIP_API int vips_hip_morph_gen(const VipsHipRegion *in, const VipsHipRegion
 VIPS_HIP_API void vips_hip_rank_need(int window_height, int top, int height, int *in_top, int *in_height);
 VIPS_HIP_API int vips_hip_rank_step(int what);
 
+/* ---------------------------------------------------------- local histogram equalisation, statistical differencing
+ *
+ * The region forms of vips_hist_local and vips_stdif, in the shape of vips_hip_rank_gen: @in and @out are windows of
+ * images of the same size and bands, both uchar (other formats: "image must be VIPS_FORMAT_UCHAR", the reference's words, with the format named); @in
+ * holds what @out reads, clipped to the image.  Output element (x, y, b) looks at the @width x @height window whose
+ * top-left is input pel (x - width / 2, y - height / 2), band b.  "window too large" when width > im_width or height >
+ * im_height, in the reference's words.  Both read the rows vips_hip_rank_need() names (window_height = @height).
+ *
+ * vips_hist_local_generate (histogram/hist_local.c:142-270): the image is embedded with VIPS_EXTEND_MIRROR (:301-306:
+ * reflected about its edge, the edge pel repeated; a window is never larger than the image, so a coordinate reflects
+ * once, and a reflected row or column always lies inside the rows and columns named above).  t = the pel itself,
+ * hist = the histogram of the window.  @max_slope 0: sum = the count of window elements <= t.  @max_slope 1 .. 100
+ * (CLAHE, :211-238): sum = sum over v <= t of min(hist[v], max_slope) + (t + 1) * (what the clip took off all 256
+ * bins) / 256, in int arithmetic in that order.  out = 255 * sum / (width * height), an int division.
+ * Two kernel families: hist_local_count (max_slope 0 and width * height <= 64: compares over the tile in LDS, no
+ * histogram) and hist_local_slide (everything else: the reference's sliding histogram, one a lane, 256 bins of 16
+ * bits in LDS).  The sliding kernel takes windows of up to 65535 pels (a bin is 16 bits), 256 a side, up to 16 bands,
+ * whose tile -- 8 + height - 1 rows of (16 / bands * 16 + width - 1) * bands bytes -- fits the 96 KB the bins leave of
+ * a CU's LDS; what does not fit is refused with the sizes in the message.  vips_hip_hist_local_step: 0 the pels of a
+ * run, 1 the rows a block of the sliding kernel makes (its tile is (3: lanes a row) / bands runs wide), 2 the largest
+ * window side, 4 the largest window area of the counting kernel, 5 / 6 the elements of a row / rows a block of it makes.
+ *
+ * vips_stdif_generate (histogram/stdif.c:135-253): the image is embedded with VIPS_EXTEND_COPY (:284-289).  sum and
+ * sum2 of the window are unsigned int; then, in double and in this order, with no fused multiply-add, correctly
+ * rounded division and square root (:208-217): mean = sum / n, var = sum2 / n - mean * mean, sig = sqrt(var),
+ * res = a * m0 + (1 - a) * mean + (t - mean) * (b * s0 / (s0 + b * sig)).  out = 0 for res < 0, 255 for res >= 256,
+ * else (unsigned char) (res + 0.5) -- where 255.5 <= res < 256 converts 256.x to a byte: the reference's machine
+ * (x86-64: cvttsd2si, then the low byte) stores 0, and so does the kernel.  s0 + b * sig == 0 divides by zero:
+ * undefined, as in the reference.  Windows of more than 66051 pels are refused: above that sum2 wraps in the reference
+ * and its result is its overflow.  One kernel, stdif_u8: column sums in LDS, then `width` of them an element.
+ * vips_hip_stdif_step: 0 / 1 the elements of a row / rows (at most) a block makes, 2 the largest window area.
+ */
+VIPS_HIP_API int vips_hip_hist_local_gen(const VipsHipRegion *in, const VipsHipRegion *out, int width, int height, int max_slope);
+VIPS_HIP_API int vips_hip_hist_local_step(int what);
+VIPS_HIP_API int vips_hip_stdif_gen(const VipsHipRegion *in, const VipsHipRegion *out, int width, int height,
+	double a, double m0, double b, double s0);
+VIPS_HIP_API int vips_hip_stdif_step(int what);
+
 /* ---------------------------------------------------------- edge detectors
  *
  * vips_sobel, vips_scharr and vips_prewitt (convolution/edge.c): a fixed 3 x 3 mask and its rot90 over the image,
@@ -778,6 +816,43 @@ VIPS_HIP_API int vips_hip_hist_find(VipsHipImage *in, VipsHipImage **out, int ba
  * tests that want sizes round it (0: the bytes of a row a wave takes in a step; 1: the rows a block takes). */
 VIPS_HIP_API int vips_hip_hist_rects(VipsHipImage *in, const int *rects, int n, unsigned int *counts);
 VIPS_HIP_API int vips_hip_hist_step(int what);
+/* vips_maplut (histogram/maplut.c:612-760) of a uchar image: out = lut[in], band by band.  @lut is an image one row
+ * or one column of n <= 256 entries (vips_check_hist's messages; more entries are index formats this path does not
+ * have: refused), any non-complex format, of 1 band, of @in's bands, or of any bands when @in has one.  An index
+ * above n - 1 reads entry n - 1 (maplut.c's clp).  The output has the LUT's format, and the LUT's bands unless the LUT
+ * has one band, then @in's.  @band >= 0 with a one-band LUT maps that band and sends the others through the identity
+ * of n entries (PACK_TABLE, :562-581: they are clipped to n - 1 too); -1 otherwise.
+ * Interpretation (:656-669): the LUT's when it has more than one band, else @in's; then vips_image_guess_interpretation
+ * of the result: a tag that cannot be true of it -- MULTIBAND always, HISTOGRAM on an image more than one pel wide and
+ * high, 16-bit tags on 8-bit pels, fewer bands than the tag needs -- gives way to the default for the format and bands
+ * (B_W / sRGB, GREY16 / RGB16 for ushort, MULTIBAND above four bands).
+ * One kernel, maplut_u8: the table (at most 256 x 4 bands x 8 bytes, larger ones are refused) in LDS, 16-byte loads
+ * of the input, whole-dword stores. */
+VIPS_HIP_API int vips_hip_maplut(VipsHipImage *in, VipsHipImage *lut, VipsHipImage **out, int band);
+/* vips_hist_cum (histogram/hist_cum.c:72-167) and vips_hist_norm (hist_norm.c:74-125) of the one-row UINT histograms
+ * vips_hip_hist_find and vips_hip_hist_cum make (other images are refused, with their format in the message).  A
+ * histogram is 256 x bands numbers: downloaded, worked out on the host, uploaded; no kernel.  The *_host forms are the
+ * arithmetic alone, on @width pels of @bands counters in host memory.  hist_norm restates the reference step by step:
+ * vips_stats' maximum of each band; a = (width - 1) / max in double; vips_linear -- a[k] * (float) p[i] + b[k] stored as
+ * a float (LOOPN, arithmetic/linear.c:227-236), or, when every band has the same maximum, the constants as floats and
+ * float arithmetic (LOOP1, :213-223) -- so counts above 2^24 lose the bits the reference loses; vips_cast to the
+ * smallest unsigned format that holds width - 1 (uchar up to 256 pels), which vips_hip_hist_norm_host returns (-1 for a null argument); @out
+ * takes elements of that format.  A band of zeros divides by zero: undefined. */
+VIPS_HIP_API int vips_hip_hist_cum(VipsHipImage *in, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_hist_norm(VipsHipImage *in, VipsHipImage **out);
+VIPS_HIP_API void vips_hip_hist_cum_host(const unsigned int *in, int width, int bands, unsigned int *out);
+VIPS_HIP_API int vips_hip_hist_norm_host(const unsigned int *in, int width, int bands, void *out);
+/* vips_hist_equal (hist_equal.c:74-98): hist_find(@band) -> hist_cum -> hist_norm -> cast to the input's format ->
+ * maplut, for uchar images of 1 .. 4 bands (vips_hip_hist_find's limits; others are refused by name).  @band -1: every
+ * band through its own table; @band k: the one table of band k, mx + 1 entries wide, on every band with the clip.
+ * Two launches an image -- the histogram kernel and maplut_u8 -- and one round trip of 1 KB a band between them. */
+VIPS_HIP_API int vips_hip_hist_equal(VipsHipImage *in, VipsHipImage **out, int band);
+/* vips_hist_local (hist_local.c:272-333) and vips_stdif (stdif.c:255-320) on whole images: see
+ * vips_hip_hist_local_gen / vips_hip_stdif_gen above.  The result has the size, bands and interpretation of the input.
+ * The class defaults: max_slope 0; a 0.5, m0 128, b 0.5, s0 50. */
+VIPS_HIP_API int vips_hip_hist_local(VipsHipImage *in, VipsHipImage **out, int width, int height, int max_slope);
+VIPS_HIP_API int vips_hip_stdif(VipsHipImage *in, VipsHipImage **out, int width, int height,
+	double a, double m0, double b, double s0);
 /* vips_smartcrop (conversion/smartcrop.c:322-437): @width x @height pels of @in, placed by @interesting (a
  * VipsInteresting: 0 none, 1 centre, 2 entropy, 3 attention, 4 low, 5 high, 6 all).  @left, @top (where the
  * crop was taken), @attention_x, @attention_y (the point the attention mode found; 0 for the others) may be NULL.

@@ -278,6 +278,19 @@ _SIGNATURES = {
     "vips_hip_hist_rects": (c_int, [c_void_p, P(c_int), c_int, P(ctypes.c_uint)]),
     "vips_hip_hist_step": (c_int, [c_int]),
     "vips_hip_smartcrop": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, P(c_int), P(c_int), P(c_int), P(c_int)]),
+    # maplut, hist_cum / hist_norm / hist_equal, hist_local, stdif
+    "vips_hip_maplut": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int]),
+    "vips_hip_hist_cum": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_hist_norm": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_hist_cum_host": (None, [P(ctypes.c_uint), c_int, c_int, P(ctypes.c_uint)]),
+    "vips_hip_hist_norm_host": (c_int, [P(ctypes.c_uint), c_int, c_int, c_void_p]),
+    "vips_hip_hist_equal": (c_int, [c_void_p, P(c_void_p), c_int]),
+    "vips_hip_hist_local_gen": (c_int, [RegionP, RegionP, c_int, c_int, c_int]),
+    "vips_hip_hist_local_step": (c_int, [c_int]),
+    "vips_hip_hist_local": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int]),
+    "vips_hip_stdif_gen": (c_int, [RegionP, RegionP, c_int, c_int, c_double, c_double, c_double, c_double]),
+    "vips_hip_stdif_step": (c_int, [c_int]),
+    "vips_hip_stdif": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_double, c_double, c_double, c_double]),
     # rank / median / morph
     "vips_hip_rank_gen": (c_int, [RegionP, RegionP, c_int, c_int, c_int]),
     "vips_hip_morph_gen": (c_int, [RegionP, RegionP, P(c_double), c_int, c_int, c_int]),

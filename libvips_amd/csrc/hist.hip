@@ -158,6 +158,183 @@ int hist_rects(const char *domain, const _VipsHipImage *in, const HistRect *rect
 	return 0;
 }
 
+// ---- vips_maplut (histogram/maplut.c) of a uchar image
+//
+//   maplut_u8<ES>  ES = 1, 2, 4, 8 bytes a table entry.  The table -- up to 256 entries x 4 tables x 8 bytes -- is
+//                  copied to LDS once a block; then, as above, a WAVE owns a row at a time and lane l the 16 input
+//                  bytes at the row's first byte rounded down to 16 + 16 l: one global_load_dwordx4 inside the row,
+//                  byte loads for the bytes inside at either end.  Every input byte is clipped to n - 1 (maplut.c's
+//                  clp) and looked up; input element q of a row goes through table q % tables (one table: every
+//                  element through it), or, a one-band image through `spread` tables, through each of them in turn.
+//                  A lane's results are consecutive bytes of the output row: 4- and 8-byte entries are stored as
+//                  dwords; 1- and 2-byte entries are gathered in a register pair and leave as whole dwords from the
+//                  first 4-byte boundary on -- only what lies before it, and what is left at the end, goes entry by
+//                  entry, and no two lanes ever write the same dword's bytes twice.
+
+constexpr int MAPLUT_THREADS = 256;
+constexpr int MAPLUT_WAVES = MAPLUT_THREADS / 64;
+constexpr int MAPLUT_GRID_BLOCKS = 1024;
+
+template <int ES>
+struct MaplutOut {
+	unsigned long long pos; // where the next byte goes
+	unsigned long long acc;
+	int held; // bytes in acc
+
+	__device__ __forceinline__ void unit(unsigned int v)
+	{
+		if constexpr (ES == 1)
+			gstore8(gptr_out_of(pos), (unsigned char) v);
+		else
+			gstore16(gptr_out_of(pos), (unsigned short) v);
+		pos += ES;
+	}
+	__device__ __forceinline__ void put(const unsigned int (&v)[2])
+	{
+		if constexpr (ES >= 4) {
+			gstore32(gptr_out_of(pos), v[0]);
+			if constexpr (ES == 8)
+				gstore32(gptr_out_of(pos + 4), v[1]);
+			pos += ES;
+		}
+		else if (held == 0 && (pos & 3) != 0)
+			unit(v[0]);
+		else {
+			acc |= (unsigned long long) v[0] << (8 * held);
+			held += ES;
+			if (held >= 4) {
+				gstore32(gptr_out_of(pos), (unsigned int) acc);
+				pos += 4;
+				acc >>= 32;
+				held -= 4;
+			}
+		}
+	}
+	__device__ __forceinline__ void flush()
+	{
+		if constexpr (ES < 4)
+			for (; held > 0; held -= ES) {
+				unit((unsigned int) acc & (ES == 1 ? 0xffu : 0xffffu));
+				acc >>= 8 * ES;
+			}
+	}
+};
+
+template <int ES>
+VH_DEV void maplut_entry(const unsigned int *table, unsigned int k, unsigned int (&v)[2])
+{
+	if constexpr (ES == 1)
+		v[0] = (table[k >> 2] >> (8 * (k & 3))) & 0xffu;
+	else if constexpr (ES == 2)
+		v[0] = (table[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+	else if constexpr (ES == 4)
+		v[0] = table[k];
+	else {
+		v[0] = table[2 * k];
+		v[1] = table[2 * k + 1];
+	}
+}
+
+template <int ES>
+__global__ void __launch_bounds__(MAPLUT_THREADS)
+maplut_kernel(MaplutArgs a)
+{
+	__shared__ unsigned int table[MAPLUT_TABLE_MAX / 4];
+	const int tid = (int) threadIdx.x;
+	const int lane = tid & 63;
+	const int wave = wave_index();
+
+	// (the table's block is whole dwords)
+	const int table_dwords = (a.n * a.tables * ES + 3) / 4;
+	for (int i = tid; i < table_dwords; i += MAPLUT_THREADS)
+		table[i] = gload32(gptr_in_of((unsigned long long) a.table), 4u * (unsigned int) i);
+	__syncthreads();
+
+	const unsigned int clip = (unsigned int) a.n - 1u;
+	const int all_waves = (int) gridDim.x * MAPLUT_WAVES;
+	for (int y = (int) blockIdx.x * MAPLUT_WAVES + wave; y < a.height; y += all_waves) {
+		const unsigned long long start = (unsigned long long) a.in + (unsigned long long) y * (unsigned long long) a.in_stride;
+		const unsigned long long orow = (unsigned long long) a.out + (unsigned long long) y * (unsigned long long) a.out_stride;
+		const int sh = (int) (start & (HIST_GROUP - 1));
+		const gptr_in base = gptr_in_of(start - sh);
+		const int groups = (sh + a.in_elems + HIST_GROUP - 1) / HIST_GROUP;
+		for (int g = lane; g < groups; g += 64) {
+			const int q0 = HIST_GROUP * g - sh; // where in the row the group's first byte is
+			unsigned int w[4] = { 0, 0, 0, 0 };
+			if (q0 >= 0 && q0 + HIST_GROUP <= a.in_elems)
+				gload128(base, (unsigned int) (HIST_GROUP * g), w);
+			else {
+#pragma unroll
+				for (int i = 0; i < HIST_GROUP; i++) {
+					const int q = q0 + i;
+					if (q >= 0 && q < a.in_elems)
+						w[i >> 2] |= (unsigned int) gload8(base, (unsigned int) (HIST_GROUP * g + i)) << (8 * (i & 3));
+				}
+			}
+			const int first = q0 < 0 ? 0 : q0; // the first element of the row this lane makes
+			MaplutOut<ES> out = { orow + (unsigned long long) first * (unsigned long long) (a.spread * ES), 0, 0 };
+			int z = a.tables > 1 && a.spread == 1 ? first % a.tables : 0;
+#pragma unroll
+			for (int i = 0; i < HIST_GROUP; i++) {
+				const int q = q0 + i;
+				if (q >= 0 && q < a.in_elems) {
+					unsigned int v = (w[i >> 2] >> (8 * (i & 3))) & 255u;
+					v = v > clip ? clip : v;
+					unsigned int e[2];
+					if (a.spread > 1) {
+						for (int zz = 0; zz < a.spread; zz++) {
+							maplut_entry<ES>(table, v * (unsigned int) a.tables + (unsigned int) zz, e);
+							out.put(e);
+						}
+					}
+					else {
+						maplut_entry<ES>(table, v * (unsigned int) a.tables + (unsigned int) z, e);
+						out.put(e);
+						z = z + 1 >= a.tables ? 0 : z + 1;
+					}
+				}
+			}
+			out.flush();
+		}
+	}
+}
+
+template <int ES>
+static int maplut_launch(const MaplutArgs &a)
+{
+	int bx = (a.height + MAPLUT_WAVES - 1) / MAPLUT_WAVES;
+	bx = bx > MAPLUT_GRID_BLOCKS ? MAPLUT_GRID_BLOCKS : bx;
+	{
+		Gate gate("maplut_u8");
+		hipLaunchKernelGGL((maplut_kernel<ES>), dim3(bx, 1, 1), dim3(MAPLUT_THREADS, 1, 1), 0, stream(), a);
+	}
+	VH_CHECK(hipGetLastError());
+	return 0;
+}
+
+// Everything has been checked (ops_histogram.cpp).
+int maplut_run(const char *domain, MaplutArgs a)
+{
+	if (a.n < 1 || a.n > 256 || a.tables < 1 || a.spread < 1 || (a.spread > 1 && a.spread != a.tables) ||
+		(long long) a.n * a.tables * a.es > MAPLUT_TABLE_MAX) {
+		error(domain, "a table of %d entries x %d bands x %d bytes: the kernel keeps up to %d bytes", a.n, a.tables, a.es, MAPLUT_TABLE_MAX);
+		return -1;
+	}
+	if ((long long) a.in_elems * a.spread * a.es >= (1LL << 31) - 64) {
+		error(domain, "image too large");
+		return -1;
+	}
+	switch (a.es) {
+	case 1: return maplut_launch<1>(a);
+	case 2: return maplut_launch<2>(a);
+	case 4: return maplut_launch<4>(a);
+	case 8: return maplut_launch<8>(a);
+	default:
+		error(domain, "table entries of %d bytes", a.es);
+		return -1;
+	}
+}
+
 } // namespace vh
 
 extern "C" {

@@ -185,6 +185,33 @@ struct NbArgs {
 	int index;        // rank: the index-th smallest
 	unsigned int key_xor;
 };
+// hist.hip: vips_maplut of a uchar image through a packed table in device memory (ops_histogram.cpp checks everything
+// and packs it): entry (v, z) -- index v < n, table z < tables -- is the `es` bytes at table[(v * tables + z) * es].  Output
+// element o of a row comes from input element o / spread through table o % tables (tables 1: every element through
+// the one table; spread > 1: a one-band image through `spread` tables).
+constexpr int MAPLUT_TABLE_MAX = 256 * 4 * 8; // bytes: what the kernel keeps in LDS
+struct MaplutArgs {
+	const unsigned char *in;
+	unsigned char *out;
+	const unsigned char *table; // device memory, n * tables * es bytes
+	long long in_stride, out_stride; // bytes
+	int in_elems;  // of a row of the input
+	int height;
+	int n, tables, es, spread;
+};
+int maplut_run(const char *domain, MaplutArgs a);
+// hist_local.hip: vips_hist_local and vips_stdif on checked regions of uchar images (ops_histogram.cpp, nb_geometry).
+// hist_local_tile: 0 the pels of a run, 1 the rows a block of the sliding kernel makes, 2 the largest window side,
+// 3 the lanes of a block that share a row, 4 the largest window area of the counting kernel.
+int hist_local_run(const char *domain, NbArgs a, int max_slope);
+int hist_local_tile(int what);
+struct StdifArgs {
+	NbArgs nb;
+	double f1, f2, f3, s0, b; // stdif.c:170-172: a * m0, 1 - a, b * s0
+	int rows;                 // output rows a block makes
+};
+int stdif_run(const char *domain, StdifArgs a);
+int stdif_tile(int what); // 0 / 1: elements of a row / rows (at most) a block makes, 2: the largest window area
 int rank_run(const char *domain, NbArgs a, int format);
 int morph_run(const char *domain, NbArgs a, const unsigned char *mask, int dilate);
 int rank_tile(int what);

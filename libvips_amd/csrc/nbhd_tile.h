@@ -1,4 +1,5 @@
-// The halo tile of the neighbourhood filters (rank.hip, morph.hip): what a block stages in LDS before it filters.
+// The halo tile of the neighbourhood filters (rank.hip, morph.hip, edge.hip, hist_local.hip): what a block stages in LDS
+// before it filters.
 //
 // A block makes TW elements x TH rows of the output.  Output element e (an element is one band of one pel) of row y
 // reads the input elements e + (i - win_w / 2) * bands, i = 0 .. win_w - 1, of rows y + j - win_h / 2, j = 0 ..
@@ -14,6 +15,8 @@
 // Elements are stored as KEYS: `key_xor` is XORed on every dword (the sign bits of a signed format, so that unsigned
 // order is the format's order; all ones on top to turn a maximum into a minimum; 0 for morph), and float keys are
 // the usual sign flip.  The callers turn a key back with nb_unkey().
+// nb_stage<.., MIRROR = true> reflects at the image's edges instead of copying them: vips_embed(VIPS_EXTEND_MIRROR), which
+// vips_hist_local puts in front (hist_local.c:301-306).
 #ifndef VH_NBHD_TILE_H
 #define VH_NBHD_TILE_H
 
@@ -49,10 +52,23 @@ VH_DEV unsigned int nb_load_element(gptr_in row, unsigned int off)
 }
 
 VH_DEV int nb_clamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+// vips_embed(VIPS_EXTEND_MIRROR) (conversion/embed.c): the image reflected about its edge, the edge pel repeated;
+// one reflection (a window is never larger than the image), then the clamp for what nobody reads
+VH_DEV int nb_mirror(int v, int size)
+{
+	v = v < 0 ? -1 - v : v >= size ? 2 * size - 1 - v : v;
+	return nb_clamp(v, 0, size - 1);
+}
+template <bool MIRROR>
+VH_DEV int nb_edge(int v, int size)
+{
+	return MIRROR ? nb_mirror(v, size) : nb_clamp(v, 0, size - 1);
+}
 
 // Stage `rows` rows, the first one image row y_start (before clamping), LDS byte 0 of each image element e_start.
-// ES: bytes an element.  Every thread of the block calls it; the caller puts the barrier behind it.
-template <int ES, bool KEYF>
+// ES: bytes an element.  MIRROR: the edge is vips_embed's mirror instead of its copy (hist_local.hip).  Every thread
+// of the block calls it; the caller puts the barrier behind it.
+template <int ES, bool KEYF, bool MIRROR = false>
 VH_DEV void nb_stage(const NbArgs &a, unsigned int *lds, int e_start, int y_start, int rows, int nthreads)
 {
 	constexpr int EPG = 16 / ES; // elements a 16-byte group
@@ -60,7 +76,7 @@ VH_DEV void nb_stage(const NbArgs &a, unsigned int *lds, int e_start, int y_star
 	const int win_e0 = a.in_left * a.bands, win_e1 = (a.in_left + a.in_width) * a.bands;
 	for (int idx = tid(); idx < rows * groups; idx += nthreads) {
 		const int r = idx / groups, g = idx - r * groups;
-		int y = nb_clamp(y_start + r, 0, a.im_height - 1);
+		int y = nb_edge<MIRROR>(y_start + r, a.im_height);
 		y = nb_clamp(y, a.in_top, a.in_top + a.in_height - 1);
 		const unsigned long long row = (unsigned long long) a.in + (unsigned long long) (y - a.in_top) * (unsigned long long) a.in_stride;
 		const gptr_in rowp = gptr_in_of(row);
@@ -82,7 +98,7 @@ VH_DEV void nb_stage(const NbArgs &a, unsigned int *lds, int e_start, int y_star
 				const int ee = e0 + k;
 				int band = ee % a.bands;
 				band = band < 0 ? band + a.bands : band;
-				int pel = nb_clamp((ee - band) / a.bands, 0, a.im_width - 1);
+				int pel = nb_edge<MIRROR>((ee - band) / a.bands, a.im_width);
 				pel = nb_clamp(pel, a.in_left, a.in_left + a.in_width - 1);
 				const unsigned int off = (unsigned int) ((pel - a.in_left) * a.bands + band) * ES;
 				w[(k * ES) >> 2] |= nb_load_element<ES>(rowp, off) << (8 * ((k * ES) & 3));

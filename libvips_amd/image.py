@@ -361,6 +361,39 @@ class Image(object):
         check(lib.vips_hip_hist_rects(self._h, flat, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint))))
         return out
 
+    # libvips/histogram: vips_hist_cum / vips_hist_norm / vips_hist_equal / vips_maplut / vips_hist_local / vips_stdif
+    def hist_cum(self):
+        """The cumulative histogram of a one-row uint histogram (what hist_find makes), band by band."""
+        return self._unary(lib.vips_hip_hist_cum)
+
+    def hist_norm(self):
+        """vips_hist_norm of a one-row uint histogram: every band scaled so that its maximum is width - 1, in the
+        smallest unsigned format that holds it (uchar for the 256 entries of a uchar image)."""
+        return self._unary(lib.vips_hip_hist_norm)
+
+    def hist_equal(self, band=-1):
+        """Global histogram equalisation of a uchar image: every band through its own cumulative histogram, or
+        (``band=k``) every band through band k's."""
+        return self._unary(lib.vips_hip_hist_equal, int(band))
+
+    def maplut(self, lut, band=-1):
+        """out = lut[in] for a uchar image: ``lut`` is an Image one row or column of up to 256 entries, of any
+        non-complex format, of one band, this image's bands, or any bands when this image has one.  ``band=k`` with a
+        one-band LUT maps band k only.  The result has the LUT's format."""
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_maplut(self._h, lut._h, ctypes.byref(out), int(band)))
+        return Image(out.value)
+
+    def hist_local(self, width, height, max_slope=0):
+        """Local histogram equalisation over ``width`` x ``height`` windows (uchar, edges mirrored); ``max_slope`` 1
+        .. 100 limits the contrast gain (CLAHE)."""
+        return self._unary(lib.vips_hip_hist_local, int(width), int(height), int(max_slope))
+
+    def stdif(self, width, height, a=0.5, m0=128.0, b=0.5, s0=50.0):
+        """Statistical differencing over ``width`` x ``height`` windows (uchar, edges copied): pull the local mean
+        towards ``m0`` (weight ``a``) and the local deviation towards ``s0`` (weight ``b``)."""
+        return self._unary(lib.vips_hip_stdif, int(width), int(height), float(a), float(m0), float(b), float(s0))
+
     def smartcrop(self, width, height, interesting="attention", with_options=False):
         """vips_smartcrop.  ``with_options``: also return ``{"left", "top", "attention_x", "attention_y"}``: where
         the crop was taken and, for the attention mode, the point it found."""
