@@ -2243,3 +2243,362 @@ vips_rotate_hip_init(VipsRotateHip *affine)
 {
 	vips_affine_hip_init(affine);
 }
+
+/* embed_hip / gravity_hip: conversion/embed.c:537-661, :702-860.  The region form (vips_hip_embed_gen) works in
+ * whole-canvas coordinates, so an image over the HBM budget goes through in row strips that read the rows
+ * vips_hip_embed_need names: for repeat and mirror a strip of border reaches back across the image.  The original's
+ * build has checked the arguments by then ("bad dimensions", the vector's length: hip_twin_header), in its own words.
+ * (insert and join take two images and these classes take one: they have no class here.) */
+typedef struct _VipsEmbedHip {
+	VipsHipOp parent_instance;
+	int x, y, width, height;
+	VipsCompassDirection direction;
+	VipsExtend extend;
+	VipsArrayDouble *background;
+} VipsEmbedHip;
+
+typedef VipsEmbedHip VipsGravityHip;
+
+typedef struct _EmbedStrip {
+	int x, y, extend;
+	unsigned char ink[32];
+} EmbedStrip;
+
+static int
+embed_hip_arguments(VipsHipOp *op, VipsHipEmbed *a)
+{
+	const char *nick = VIPS_OBJECT_GET_CLASS(op)->nickname;
+	VipsEmbedHip *embed = (VipsEmbedHip *) op;
+
+	vips_hip_embed_defaults(a);
+	a->extend = embed->extend;
+	a->extend_set = vips_object_argument_isset(VIPS_OBJECT(op), "extend");
+	if (vips_object_argument_isset(VIPS_OBJECT(op), "background") && embed->background) {
+		int n;
+		const double *v = vips_array_double_get(embed->background, &n);
+
+		if (n > VIPS_HIP_CANVAS_MAX_BACKGROUND) {
+			vips_error(nick, "%s", "background too long");
+			return -1;
+		}
+		a->n_background = n;
+		memcpy(a->background, v, n * sizeof(double));
+	}
+
+	return 0;
+}
+
+static int
+embed_hip_position(VipsHipOp *op, int in_width, int in_height, int *x, int *y)
+{
+	VipsEmbedHip *embed = (VipsEmbedHip *) op;
+
+	if (strcmp(VIPS_OBJECT_GET_CLASS(op)->nickname, "gravity_hip") == 0) {
+		if (vips_hip_gravity_position(embed->direction, in_width, in_height, embed->width, embed->height, x, y))
+			return hip_fail("gravity_hip");
+	}
+	else {
+		*x = embed->x;
+		*y = embed->y;
+	}
+
+	return 0;
+}
+
+static int
+vips_embed_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsEmbedHip *embed = (VipsEmbedHip *) op;
+	VipsHipEmbed a;
+
+	if (embed_hip_arguments(op, &a))
+		return -1;
+	if (strcmp(VIPS_OBJECT_GET_CLASS(op)->nickname, "gravity_hip") == 0)
+		return vips_hip_gravity(in, out, embed->direction, embed->width, embed->height, &a);
+
+	return vips_hip_embed(in, out, embed->x, embed->y, embed->width, embed->height, &a);
+}
+
+static void
+vips_embed_hip_strip_close(VipsHipOp *op, void *plan)
+{
+	g_free(plan);
+}
+
+static int
+vips_embed_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	const char *nick = VIPS_OBJECT_GET_CLASS(op)->nickname;
+	VipsEmbedHip *embed = (VipsEmbedHip *) op;
+	VipsHipEmbed a;
+	EmbedStrip *p;
+	int mode;
+
+	if (embed_hip_arguments(op, &a))
+		return -1;
+	p = g_new0(EmbedStrip, 1);
+	if (embed_hip_position(op, in->Xsize, in->Ysize, &p->x, &p->y) ||
+		vips_hip_embed_plan(nick, &a, in->Xsize, in->Ysize, in->Bands, in->BandFmt, in->Type, p->x, p->y,
+			embed->width, embed->height, &mode, &p->extend, p->ink)) {
+		g_free(p);
+		return hip_fail(nick);
+	}
+	/* the copy has no region form */
+	if (!mode) {
+		g_free(p);
+		return 1;
+	}
+	*plan = p;
+
+	return 0;
+}
+
+static void
+vips_embed_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	EmbedStrip *p = (EmbedStrip *) plan;
+	int need[4];
+
+	vips_hip_embed_need(p->extend, op->ready->Xsize, op->ready->Ysize, p->x, p->y, 0, out_top, op->out->Xsize, out_rows, need);
+	/* (a strip of nothing but ink reads no row: any one will do) */
+	*in_top = need[3] > 0 ? need[1] : 0;
+	*in_rows = need[3] > 0 ? need[3] : 1;
+}
+
+static int
+vips_embed_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	EmbedStrip *p = (EmbedStrip *) plan;
+
+	return vips_hip_embed_gen(p->extend, p->ink, p->x, p->y, in, out);
+}
+
+#define vips_gravity_hip_compute vips_embed_hip_compute
+#define vips_gravity_hip_strip_open vips_embed_hip_strip_open
+#define vips_gravity_hip_strip_need vips_embed_hip_strip_need
+#define vips_gravity_hip_strip_run vips_embed_hip_strip_run
+#define vips_gravity_hip_strip_close vips_embed_hip_strip_close
+
+HIP_SUBCLASS_FULL(VipsEmbedHip, vips_embed_hip, "embed_hip", "embed an image in a larger image (MI355X)", HIP_STRIPS(vips_embed_hip))
+HIP_SUBCLASS_FULL(VipsGravityHip, vips_gravity_hip, "gravity_hip", "place an image within a larger image with a certain gravity (MI355X)",
+	HIP_STRIPS(vips_gravity_hip))
+
+static void
+embed_hip_common_args(VipsHipOpClass *class)
+{
+	VIPS_ARG_INT(class, "width", 5, "Width", "Image width in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsEmbedHip, width), 1, 1000000000, 1);
+	VIPS_ARG_INT(class, "height", 6, "Height", "Image height in pixels",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsEmbedHip, height), 1, 1000000000, 1);
+	VIPS_ARG_ENUM(class, "extend", 7, "Extend", "How to generate the extra pixels",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsEmbedHip, extend), VIPS_TYPE_EXTEND, VIPS_EXTEND_BLACK);
+	VIPS_ARG_BOXED(class, "background", 12, "Background", "Color for background pixels",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsEmbedHip, background), VIPS_TYPE_ARRAY_DOUBLE);
+}
+
+static void
+vips_embed_hip_args(VipsEmbedHipClass *class)
+{
+	VIPS_ARG_INT(class, "x", 3, "x", "Left edge of input in output",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsEmbedHip, x), -1000000000, 1000000000, 0);
+	VIPS_ARG_INT(class, "y", 4, "y", "Top edge of input in output",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsEmbedHip, y), -1000000000, 1000000000, 0);
+	embed_hip_common_args(class);
+}
+
+static void
+vips_gravity_hip_args(VipsGravityHipClass *class)
+{
+	VIPS_ARG_ENUM(class, "direction", 3, "Direction", "Direction to place image within width/height",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsEmbedHip, direction), VIPS_TYPE_COMPASS_DIRECTION,
+		VIPS_COMPASS_DIRECTION_CENTRE);
+	embed_hip_common_args(class);
+}
+
+static void
+vips_embed_hip_init(VipsEmbedHip *embed)
+{
+	embed->extend = VIPS_EXTEND_BLACK;
+	embed->background = vips_array_double_newv(1, 0.0);
+}
+
+static void
+vips_gravity_hip_init(VipsGravityHip *embed)
+{
+	vips_embed_hip_init(embed);
+}
+
+/* flatten_hip / addalpha_hip: conversion/flatten.c:531-575, addalpha.c:73-99.  Pointwise: an image over the HBM budget
+ * goes through in row strips of the same rows.  flatten_hip's strips run the region form, vips_hip_flatten_gen,
+ * straight into the strip's output; an integer image whose max_alpha is below its format's range (flatten.c:457-470)
+ * is cast to double, flattened and cast back on the strip's window, three region calls.  A one-band image is a copy
+ * and has no region form. */
+typedef struct _VipsFlattenHip {
+	VipsHipOp parent_instance;
+	VipsArrayDouble *background;
+	double max_alpha;
+} VipsFlattenHip;
+
+typedef struct _FlattenStrip {
+	double max_alpha;
+	int black;
+	int through_double;
+	unsigned char ink[256];
+} FlattenStrip;
+
+static int
+flatten_hip_arguments(VipsHipOp *op, VipsHipFlatten *a)
+{
+	VipsFlattenHip *flatten = (VipsFlattenHip *) op;
+
+	vips_hip_flatten_defaults(a);
+	if (flatten->background) {
+		int n;
+		const double *v = vips_array_double_get(flatten->background, &n);
+
+		if (n > VIPS_HIP_CANVAS_MAX_BACKGROUND) {
+			vips_error("flatten_hip", "%s", "background too long");
+			return -1;
+		}
+		a->n_background = n;
+		memcpy(a->background, v, n * sizeof(double));
+	}
+	a->max_alpha_set = vips_object_argument_isset(VIPS_OBJECT(op), "max_alpha");
+	a->max_alpha = flatten->max_alpha;
+
+	return 0;
+}
+
+static int
+vips_flatten_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsHipFlatten a;
+
+	if (flatten_hip_arguments(op, &a))
+		return -1;
+
+	return vips_hip_flatten(in, out, &a);
+}
+
+static void
+vips_flatten_hip_strip_close(VipsHipOp *op, void *plan)
+{
+	g_free(plan);
+}
+
+static int
+vips_flatten_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	static const double zero[1] = { 0.0 };
+	VipsHipFlatten a;
+	FlattenStrip *p;
+	const double *bg;
+	int n;
+
+	/* the copy has no region form */
+	if (in->Bands == 1)
+		return 1;
+	if (flatten_hip_arguments(op, &a))
+		return -1;
+	p = g_new0(FlattenStrip, 1);
+	p->max_alpha = a.max_alpha_set ? a.max_alpha : vips_interpretation_max_alpha(in->Type);
+	p->through_double = vips_band_format_isint(in->BandFmt) && p->max_alpha < vips_image_get_format_max(in->BandFmt);
+	n = a.n_background > 0 ? a.n_background : 1;
+	bg = a.n_background > 0 ? a.background : zero;
+	p->black = 1;
+	for (int i = 0; i < n; i++)
+		if (bg[i] != 0.0)
+			p->black = 0;
+	if (!p->black &&
+		vips_hip_vector_to_ink(bg, n, in->Bands - 1, p->through_double ? VIPS_HIP_FORMAT_DOUBLE : (int) in->BandFmt, p->ink)) {
+		g_free(p);
+		return hip_fail("flatten_hip");
+	}
+	*plan = p;
+
+	return 0;
+}
+
+static void
+vips_flatten_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	*in_top = out_top;
+	*in_rows = out_rows;
+}
+
+static int
+vips_flatten_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	FlattenStrip *p = (FlattenStrip *) plan;
+	VipsHipImage *tmp[2] = { NULL, NULL };
+	VipsHipRegion wide, flat;
+	int result = -1;
+
+	if (!p->through_double)
+		return vips_hip_flatten_gen(in, out, p->max_alpha, p->black, p->ink);
+
+	if ((tmp[0] = vips_hip_image_new(in->width, in->height, in->bands, VIPS_HIP_FORMAT_DOUBLE, 0)) &&
+		(tmp[1] = vips_hip_image_new(out->width, out->height, out->bands, VIPS_HIP_FORMAT_DOUBLE, 0))) {
+		vips_hip_image_region(tmp[0], &wide);
+		wide.left = in->left;
+		wide.top = in->top;
+		wide.im_width = in->im_width;
+		wide.im_height = in->im_height;
+		vips_hip_image_region(tmp[1], &flat);
+		flat.left = out->left;
+		flat.top = out->top;
+		flat.im_width = out->im_width;
+		flat.im_height = out->im_height;
+		if (!vips_hip_cast_gen(in, &wide) &&
+			!vips_hip_flatten_gen(&wide, &flat, p->max_alpha, p->black, p->ink) &&
+			!vips_hip_cast_gen(&flat, out))
+			result = 0;
+	}
+	for (int i = 0; i < 2; i++)
+		if (tmp[i])
+			vips_hip_image_unref(tmp[i]);
+
+	return result;
+}
+
+HIP_SUBCLASS_FULL(VipsFlattenHip, vips_flatten_hip, "flatten_hip", "flatten alpha out of an image (MI355X)",
+	HIP_STRIPS(vips_flatten_hip))
+
+static void
+vips_flatten_hip_args(VipsFlattenHipClass *class)
+{
+	VIPS_ARG_BOXED(class, "background", 2, "Background", "Background value",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsFlattenHip, background), VIPS_TYPE_ARRAY_DOUBLE);
+	VIPS_ARG_DOUBLE(class, "max_alpha", 115, "Maximum alpha", "Maximum value of alpha channel",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsFlattenHip, max_alpha), 0, 100000000, 255);
+}
+
+static void
+vips_flatten_hip_init(VipsFlattenHip *flatten)
+{
+	flatten->background = vips_array_double_newv(1, 0.0);
+	flatten->max_alpha = 255.0;
+}
+
+typedef struct _VipsAddAlphaHip {
+	VipsHipOp parent_instance;
+} VipsAddAlphaHip;
+
+static int
+vips_addalpha_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_addalpha(in, out);
+}
+
+HIP_SUBCLASS_FULL(VipsAddAlphaHip, vips_addalpha_hip, "addalpha_hip", "append an alpha channel (MI355X)",
+	class->halo = hip_pointwise_halo;)
+
+static void
+vips_addalpha_hip_args(VipsAddAlphaHipClass *class)
+{
+}
+
+static void
+vips_addalpha_hip_init(VipsAddAlphaHip *addalpha)
+{
+}

@@ -1554,7 +1554,9 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *     own sums wrap);
  *   - sobel / scharr / prewitt / compass / canny of double images, canny of pels wider than its kernel's tile holds;
  *   - affine / similarity / rotate of double images, with an interpolator other than nearest, bilinear and bicubic
- *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands.
+ *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands;
+ *   - embed / gravity of pels of more than 32 bytes (the canvas kernels' ink), flatten to a background of more than
+ *     256 bytes.
  */
 static gboolean
 hip_wants_original(VipsHipOp *op, VipsImage *in)
@@ -1607,6 +1609,11 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 		if (other || in->BandFmt == VIPS_FORMAT_DOUBLE || in->Bands * 4 > VIPS_HIP_AFFINE_MAX_PEL)
 			return TRUE;
 	}
+	if ((strcmp(nick, "embed_hip") == 0 || strcmp(nick, "gravity_hip") == 0) && VIPS_IMAGE_SIZEOF_PEL(in) > 32)
+		return TRUE;
+	if (strcmp(nick, "flatten_hip") == 0 && in->Bands > 1 &&
+		(guint64) (in->Bands - 1) * VIPS_MAX(VIPS_IMAGE_SIZEOF_ELEMENT(in), sizeof(double)) > 256)
+		return TRUE;
 	if (strcmp(nick, "thumbnail_image_hip") == 0) {
 		gboolean linear = FALSE;
 		int crop = 0;
@@ -1740,7 +1747,7 @@ vips_hip_op_init(VipsHipOp *op)
 
 /* ------------------------------------------------------------------ subclasses */
 
-/* (the 32 operation classes: arguments, defaults, hooks) */
+/* (the 36 operation classes: arguments, defaults, hooks) */
 #include "vips_hip_classes.c"
 
 /* ------------------------------------------------------------------ registration */
@@ -1783,6 +1790,10 @@ g_module_check_init(GModule *module)
 	vips_affine_hip_get_type();
 	vips_similarity_hip_get_type();
 	vips_rotate_hip_get_type();
+	vips_embed_hip_get_type();
+	vips_gravity_hip_get_type();
+	vips_flatten_hip_get_type();
+	vips_addalpha_hip_get_type();
 
 	/* types registered by a module must never be unloaded */
 	g_module_make_resident(module);

@@ -1027,6 +1027,118 @@ VIPS_HIP_API int vips_hip_similarity(VipsHipImage *in, VipsHipImage **out, doubl
 	const VipsHipAffine *args);
 VIPS_HIP_API int vips_hip_rotate(VipsHipImage *in, VipsHipImage **out, double angle, const VipsHipAffine *args);
 
+/* ------------------------------------------------ canvas and alpha: embed / gravity / insert / join, flatten, addalpha
+ *
+ * vips_embed and vips_gravity (conversion/embed.c), vips_insert (insert.c) and vips_join (join.c): exact copies of
+ * pels onto a canvas, ONE launch an operation (canvas.hip), any non-complex format, pels of up to 32 bytes.
+ * vips_flatten (flatten.c) and vips_addalpha (addalpha.c): any non-complex format and band count (a flatten ink of
+ * up to 256 bytes).  Complex images are refused with vips_check_noncomplex's words, "image must be non-complex".
+ * Results carry no orientation.
+ */
+#define VIPS_HIP_CANVAS_MAX_BACKGROUND 32
+
+/* The optional arguments of vips_embed / vips_gravity.  vips_hip_embed_defaults(): extend black, nothing set.
+ * @extend_set: the caller gave `extend`; a background without it selects extend background (embed.c:366-368).
+ * @n_background 0: not given (the class default, one zero). */
+typedef struct {
+	int extend; /* VipsHipExtend */
+	int extend_set;
+	int n_background;
+	double background[VIPS_HIP_CANVAS_MAX_BACKGROUND];
+} VipsHipEmbed;
+VIPS_HIP_API void vips_hip_embed_defaults(VipsHipEmbed *args);
+
+/* The optional arguments of vips_flatten.  Defaults: background 0 (n_background 0: not given), max_alpha from the
+ * image's interpretation (flatten.c:454). */
+typedef struct {
+	int n_background;
+	double background[VIPS_HIP_CANVAS_MAX_BACKGROUND];
+	int max_alpha_set;
+	double max_alpha;
+} VipsHipFlatten;
+VIPS_HIP_API void vips_hip_flatten_defaults(VipsHipFlatten *args);
+
+/* The optional arguments of vips_insert (expand, background) and vips_join (those, shim and align: a VipsAlign, 0 low,
+ * 1 centre, 2 high). */
+typedef struct {
+	int expand;
+	int n_background;
+	double background[VIPS_HIP_CANVAS_MAX_BACKGROUND];
+	int shim;
+	int align;
+} VipsHipInsert;
+VIPS_HIP_API void vips_hip_insert_defaults(VipsHipInsert *args);
+
+/* VipsCompassDirection, include/vips/conversion.h */
+typedef enum {
+	VIPS_HIP_COMPASS_CENTRE = 0,
+	VIPS_HIP_COMPASS_NORTH,
+	VIPS_HIP_COMPASS_EAST,
+	VIPS_HIP_COMPASS_SOUTH,
+	VIPS_HIP_COMPASS_WEST,
+	VIPS_HIP_COMPASS_NORTH_EAST,
+	VIPS_HIP_COMPASS_SOUTH_EAST,
+	VIPS_HIP_COMPASS_SOUTH_WEST,
+	VIPS_HIP_COMPASS_NORTH_WEST,
+	VIPS_HIP_COMPASS_LAST
+} VipsHipCompassDirection;
+
+/* vips__vector_to_ink (conversion/insert.c:240-363) for an image of @bands elements of @format: element z of the pel is
+ * background[n == bands ? z : 0], made a float by vips_linear and cast as vips_cast casts.  Host only.  @ink takes
+ * bands * sizeof(format) bytes.  -1 with "linear: vector must have 1 or N elements" for a vector of another length. */
+VIPS_HIP_API int vips_hip_vector_to_ink(const double *background, int n, int bands, int format, void *ink);
+
+/* vips_embed_base_build restated (embed.c:345-535): *@mode is 0 when the result is a copy of the input (the identity
+ * case), else 1; *@extend the extend mode that runs; @ink (32 bytes) the pel of black / white / background.  Errors in
+ * the reference's words after @nickname: "bad dimensions" when the image misses the canvas in black / white /
+ * background / copy (repeat and mirror take that case), the vector's length.  white is what vips_region_paint writes
+ * (iofuncs/region.c:909-956): (int) vips_interpretation_max_alpha as a memset byte for integer formats, as a value
+ * for float and double.  No device is touched. */
+VIPS_HIP_API int vips_hip_embed_plan(const char *nickname, const VipsHipEmbed *args, int in_width, int in_height,
+	int bands, int format, int interpretation, int x, int y, int width, int height, int *mode, int *extend, void *ink);
+/* Where vips_gravity puts the image (embed.c:715-790). */
+VIPS_HIP_API int vips_hip_gravity_position(int direction, int in_width, int in_height, int width, int height, int *x, int *y);
+/* The rectangle of the input image that the canvas rect (left, top, width, height) draws on, for an image of in_width
+ * x in_height at (x, y) under @extend (a VipsHipExtend): the bounding box of the pels read; need[2] or need[3] is 0
+ * when the rect is all ink. */
+VIPS_HIP_API void vips_hip_embed_need(int extend, int in_width, int in_height, int x, int y, int left, int top, int width,
+	int height, int need[4]);
+/* Fill @out, a window of the canvas (im_width x im_height its size), from @in, a window of the input image that must
+ * hold vips_hip_embed_need() of the rect ("input region too small" otherwise).  @extend and @ink as vips_hip_embed_plan
+ * gives them.  Bytes of @out's frame outside the window are not touched.  Both regions' memory must cover height *
+ * stride bytes from `data`, the last row included: where strides and `data` are multiples of 4 the streaming kernel
+ * reads whole aligned dwords, which can take in up to 3 bytes past a row's last pel -- inside that row's stride, never
+ * past it. */
+VIPS_HIP_API int vips_hip_embed_gen(int extend, const void *ink, int x, int y, const VipsHipRegion *in,
+	const VipsHipRegion *out);
+/* vips_flatten's generate (flatten.c:167-419) on a pair of windows of the same position and size: @in has one band
+ * more than @out, both of one non-complex format.  @ink: out->bands elements of that format (ignored for @black). */
+VIPS_HIP_API int vips_hip_flatten_gen(const VipsHipRegion *in, const VipsHipRegion *out, double max_alpha, int black,
+	const void *ink);
+
+/* Whole images.  @args NULL: the defaults. */
+VIPS_HIP_API int vips_hip_embed(VipsHipImage *in, VipsHipImage **out, int x, int y, int width, int height,
+	const VipsHipEmbed *args);
+VIPS_HIP_API int vips_hip_gravity(VipsHipImage *in, VipsHipImage **out, int direction, int width, int height,
+	const VipsHipEmbed *args);
+/* vips_flatten_build (flatten.c:421-529): a one-band image is a copy; integer images whose max_alpha is below the
+ * format's maximum go through double and back (vips_hip_cast); uchar images take the table kernels. */
+VIPS_HIP_API int vips_hip_flatten(VipsHipImage *in, VipsHipImage **out, const VipsHipFlatten *args);
+/* One more band holding vips_interpretation_max_alpha, cast to the format. */
+VIPS_HIP_API int vips_hip_addalpha(VipsHipImage *in, VipsHipImage **out);
+/* vips_insert_build (insert.c:365-444): vips__formatalike (the common format of arithmetic.c:76-109, vips_hip_cast)
+ * and vips__bandalike (one band against n: the band n times) first, then one launch.  Errors in the reference's
+ * words: "images must have the same number of bands, or one must be single-band". */
+VIPS_HIP_API int vips_hip_insert(VipsHipImage *main, VipsHipImage *sub, VipsHipImage **out, int x, int y,
+	const VipsHipInsert *args);
+/* vips_join_build (join.c:92-216): @direction a VipsDirection (0 horizontal, 1 vertical); without expand the cut to
+ * the smaller image is part of the same launch. */
+VIPS_HIP_API int vips_hip_join(VipsHipImage *in1, VipsHipImage *in2, VipsHipImage **out, int direction,
+	const VipsHipInsert *args);
+/* 0: the threads of a block of the canvas kernels; 1: the bytes of a group of the streaming kernel for @pel_size
+ * (0: that pel size takes the one-pel-a-lane kernel), for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_canvas_step(int what, int pel_size);
+
 #ifdef __cplusplus
 }
 #endif

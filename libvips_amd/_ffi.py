@@ -87,6 +87,41 @@ class Affine(ctypes.Structure):
     ]
 
 
+class Embed(ctypes.Structure):
+    """VipsHipEmbed (include/vips_hip.h): the optional arguments of vips_embed / vips_gravity."""
+
+    MAX_BACKGROUND = 32
+    _fields_ = [
+        ("extend", ctypes.c_int),
+        ("extend_set", ctypes.c_int),
+        ("n_background", ctypes.c_int),
+        ("background", ctypes.c_double * 32),
+    ]
+
+
+class Flatten(ctypes.Structure):
+    """VipsHipFlatten (include/vips_hip.h)."""
+
+    _fields_ = [
+        ("n_background", ctypes.c_int),
+        ("background", ctypes.c_double * 32),
+        ("max_alpha_set", ctypes.c_int),
+        ("max_alpha", ctypes.c_double),
+    ]
+
+
+class Insert(ctypes.Structure):
+    """VipsHipInsert (include/vips_hip.h): the optional arguments of vips_insert / vips_join."""
+
+    _fields_ = [
+        ("expand", ctypes.c_int),
+        ("n_background", ctypes.c_int),
+        ("background", ctypes.c_double * 32),
+        ("shim", ctypes.c_int),
+        ("align", ctypes.c_int),
+    ]
+
+
 def _load():
     # PyTorch-ROCm carries its own HIP runtime (soname libamdhip64.so).  Import it first so
     # libvipship.so, which needs that soname, binds to the SAME runtime: device pointers,
@@ -334,6 +369,24 @@ _SIGNATURES = {
     "vips_hip_affine": (c_int, [c_void_p, P(c_void_p), P(Affine)]),
     "vips_hip_similarity": (c_int, [c_void_p, P(c_void_p), c_double, c_double, P(Affine)]),
     "vips_hip_rotate": (c_int, [c_void_p, P(c_void_p), c_double, P(Affine)]),
+    # embed / gravity / insert / join, flatten, addalpha
+    "vips_hip_embed_defaults": (None, [P(Embed)]),
+    "vips_hip_flatten_defaults": (None, [P(Flatten)]),
+    "vips_hip_insert_defaults": (None, [P(Insert)]),
+    "vips_hip_vector_to_ink": (c_int, [P(c_double), c_int, c_int, c_int, c_void_p]),
+    "vips_hip_embed_plan": (c_int, [c_char_p, P(Embed), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    P(c_int), P(c_int), c_void_p]),
+    "vips_hip_gravity_position": (c_int, [c_int, c_int, c_int, c_int, c_int, P(c_int), P(c_int)]),
+    "vips_hip_embed_need": (None, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P(c_int)]),
+    "vips_hip_embed_gen": (c_int, [c_int, c_void_p, c_int, c_int, RegionP, RegionP]),
+    "vips_hip_flatten_gen": (c_int, [RegionP, RegionP, c_double, c_int, c_void_p]),
+    "vips_hip_embed": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, c_int, P(Embed)]),
+    "vips_hip_gravity": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, P(Embed)]),
+    "vips_hip_flatten": (c_int, [c_void_p, P(c_void_p), P(Flatten)]),
+    "vips_hip_addalpha": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_insert": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, c_int, P(Insert)]),
+    "vips_hip_join": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, P(Insert)]),
+    "vips_hip_canvas_step": (c_int, [c_int, c_int]),
 }
 
 MISSING = []

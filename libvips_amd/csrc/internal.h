@@ -276,4 +276,45 @@ struct AffineArgs {
 };
 // format: uchar .. int or float; interpolate: VipsHipInterpolate
 int affine_run(const char *domain, AffineArgs a, int format, int interpolate);
+// canvas.hip: vips_embed, vips_gravity, vips_insert and vips_join on checked geometry (ops_canvas.cpp checks everything):
+// ONE launch writes the rect (out_left, out_top, out_width, out_height) of a canvas.  Canvas pel (X, Y) is the sub-image's
+// pel where the sub-image lies, else the main image's pel where that lies, else -- by `mode` -- the ink, or the main
+// image's pel at the clamped (copy), clock-arithmetic (repeat) or reflected (mirror) coordinate.  `main` points at pel
+// (win_left, win_top) of the main image: the caller has checked that every pel the rect draws on lies in what it holds.
+enum { CANVAS_INK = 0, CANVAS_COPY = 1, CANVAS_REPEAT = 2, CANVAS_MIRROR = 3 };
+constexpr int CANVAS_MAX_PEL = 32; // bytes
+struct CanvasArgs {
+	const unsigned char *main;
+	const unsigned char *sub; // nullptr: none
+	unsigned char *out;       // pel (out_left, out_top) of the canvas
+	long long main_stride, sub_stride, out_stride; // bytes
+	int mx, my, mw, mh; // where the main image's pel (0, 0) lies on the canvas, its whole size
+	int win_left, win_top;
+	int sx, sy, sw, sh; // the sub-image
+	int out_left, out_top, out_width, out_height;
+	int pel;    // bytes
+	int mode;   // CANVAS_*
+	int groups; // (stream kernel) 16- / 48-byte groups of a row of the rect, the ragged one included
+	unsigned int ink[CANVAS_MAX_PEL / 4];
+};
+int canvas_run(const char *domain, CanvasArgs a);
+// canvas_tile: 0 the threads of a block, 1 the bytes of a group of the stream kernel for a pel size (0: the stream
+// kernel does not take it)
+int canvas_tile(int what, int pel);
+// ... vips_flatten's generate functions (flatten.c:167-419): `format` uchar takes the table kernels, everything else the
+// double macros; `black` the black-background path.  `ink` holds bands - 1 elements of `format`.
+constexpr int FLATTEN_MAX_INK = 256; // bytes
+struct FlattenArgs {
+	const unsigned char *in;
+	unsigned char *out;
+	long long in_stride, out_stride; // bytes
+	int width, height, bands;        // of the input
+	int black;
+	double max_alpha;
+	unsigned long long ink[FLATTEN_MAX_INK / 8];
+};
+int flatten_run(const char *domain, FlattenArgs a, int format);
+// ... vips_addalpha: every pel's `bands` elements of `es` bytes, then `alpha` (the low es bytes)
+int addalpha_run(const char *domain, const unsigned char *in, long long in_stride, unsigned char *out, long long out_stride,
+	int width, int height, int bands, int es, unsigned long long alpha);
 } // namespace vh

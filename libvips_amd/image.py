@@ -70,6 +70,10 @@ COMBINES = {"max": 0, "sum": 1, "min": 2}
 # VipsExtend (include/vips/conversion.h); the interpolators the device has (resample/interpolate.c, bicubic.cpp)
 EXTENDS = {"black": 0, "copy": 1, "repeat": 2, "mirror": 3, "white": 4, "background": 5}
 INTERPOLATORS = {"nearest": 0, "bilinear": 1, "bicubic": 2}
+# VipsCompassDirection, VipsAlign (include/vips/conversion.h)
+COMPASS_DIRECTIONS = {"centre": 0, "north": 1, "east": 2, "south": 3, "west": 4, "north-east": 5, "south-east": 6,
+                      "south-west": 7, "north-west": 8}
+ALIGNS = {"low": 0, "centre": 1, "high": 2}
 # VipsInterpretation (include/vips/image.h:94-118)
 INTERPRETATIONS = {
     "multiband": 0,
@@ -489,6 +493,77 @@ class Image(object):
 
     def rotate(self, angle, **kwargs):
         return self._unary(lib.vips_hip_rotate, float(angle), ctypes.byref(self.affine_args(**kwargs)))
+
+    # vips_embed / vips_gravity / vips_flatten / vips_addalpha / vips_insert / vips_join, with pyvips' argument names
+    @staticmethod
+    def _background(args, background, what):
+        if background is not None:
+            background = [float(v) for v in np.atleast_1d(background)]
+            if len(background) > _ffi.Embed.MAX_BACKGROUND:
+                raise _ffi.VipsHipError("%s: background of more than %d elements" % (what, _ffi.Embed.MAX_BACKGROUND))
+            args.n_background = len(background)
+            args.background[:len(background)] = background
+        return args
+
+    @classmethod
+    def embed_args(cls, extend=None, background=None):
+        """The VipsHipEmbed of these arguments: ``extend`` None means not given (a background then selects extend
+        "background", as in vips_embed)."""
+        args = _ffi.Embed()
+        lib.vips_hip_embed_defaults(ctypes.byref(args))
+        if extend is not None:
+            args.extend = _enum(EXTENDS, extend, "extend")
+            args.extend_set = 1
+        return cls._background(args, background, "embed")
+
+    def embed(self, x, y, width, height, extend=None, background=None):
+        """vips_embed: the image at (x, y) on a canvas of width x height; extend "black" (the default), "copy",
+        "repeat", "mirror", "white" or "background"."""
+        return self._unary(lib.vips_hip_embed, int(x), int(y), int(width), int(height),
+                           ctypes.byref(self.embed_args(extend, background)))
+
+    def gravity(self, direction, width, height, extend=None, background=None):
+        """vips_gravity: the image placed on the canvas by a compass direction ("centre", "north", "north-east" ...)."""
+        return self._unary(lib.vips_hip_gravity, _enum(COMPASS_DIRECTIONS, direction, "direction"), int(width), int(height),
+                           ctypes.byref(self.embed_args(extend, background)))
+
+    def flatten(self, background=None, max_alpha=None):
+        """vips_flatten: the last band blended out against ``background`` (default 0); ``max_alpha`` defaults to the
+        interpretation's (255, 65535 for 16-bit, 1 for scRGB)."""
+        args = _ffi.Flatten()
+        lib.vips_hip_flatten_defaults(ctypes.byref(args))
+        self._background(args, background, "flatten")
+        if max_alpha is not None:
+            args.max_alpha_set = 1
+            args.max_alpha = float(max_alpha)
+        return self._unary(lib.vips_hip_flatten, ctypes.byref(args))
+
+    def addalpha(self):
+        """vips_addalpha: one more band holding the interpretation's max alpha."""
+        return self._unary(lib.vips_hip_addalpha)
+
+    @classmethod
+    def _insert_args(cls, expand, background, shim=0, align="low"):
+        args = _ffi.Insert()
+        lib.vips_hip_insert_defaults(ctypes.byref(args))
+        args.expand = int(bool(expand))
+        args.shim = int(shim)
+        args.align = _enum(ALIGNS, align, "align")
+        return cls._background(args, background, "insert")
+
+    def insert(self, sub, x, y, expand=False, background=None):
+        """vips_insert: ``sub`` pasted onto this image at (x, y); formats and bands are matched as the reference does."""
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_insert(self._h, sub._h, ctypes.byref(out), int(x), int(y),
+                                  ctypes.byref(self._insert_args(expand, background))))
+        return Image(out.value)
+
+    def join(self, other, direction, expand=False, shim=0, background=None, align="low"):
+        """vips_join: ``other`` beside ("horizontal") or below ("vertical") this image."""
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_join(self._h, other._h, ctypes.byref(out), _enum(DIRECTIONS, direction, "direction"),
+                                ctypes.byref(self._insert_args(expand, background, shim, align))))
+        return Image(out.value)
 
     def conv(self, mask, scale=1.0, offset=0.0, precision="float", layers=5, cluster=1):
         m = self._mask(mask)

@@ -1,0 +1,672 @@
+"""GPU parity: canvas and alpha on the device -- vips_embed (all six extends), vips_gravity, vips_insert, vips_join,
+vips_flatten and vips_addalpha (libvips_amd/csrc/canvas.hip, ops_canvas.cpp).
+
+Four of the operations move pels and the fifth is arithmetic the reference does in float or double with separate
+multiplies and adds, so every comparison is np.array_equal against the compiled reference -- values, dtype and shape;
+nothing has a tolerance.  One-image operations reach the reference through Ref.run, vips_insert and vips_join through
+its command line.  The streaming and the one-pel-a-lane kernel are swept over pel sizes, row lengths round the
+streaming kernel's groups and a wave of them, and placements, against a numpy model of vips_embed that the reference
+pins in this file (test_the_embed_model_is_the_reference); the sweep runs on windows of larger frames, so that rows of
+any length start on dwords and what lies outside a window can be seen to stay as it was.  Every sweep case asserts by
+the gate report which kernel ran and that it was launched once.
+Runs on the CPU too, on host fibers (tests/test_emul_canvas.py)."""
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import libvips_amd
+from libvips_amd import Image, VipsHipError, _ffi
+from tests import helpers
+from tests.helpers import Ref
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")]
+
+lib = _ffi.lib
+EXTENDS = {"black": 0, "copy": 1, "repeat": 2, "mirror": 3, "white": 4, "background": 5}
+INTERP = helpers.INTERP
+VIPS = os.path.join(helpers.ROOT, "oracle", "_ref", "bin", "vips")
+# pel size -> (dtype, bands)
+PELS = {1: (np.uint8, 1), 2: (np.uint16, 1), 3: (np.uint8, 3), 4: (np.uint8, 4), 6: (np.uint16, 3), 8: (np.uint16, 4),
+        12: (np.float32, 3), 16: (np.float32, 4), 24: (np.float64, 3), 32: (np.float64, 4)}
+SENTINEL = 0xA5
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _init():
+    libvips_amd.init(0)
+
+
+class gated(object):
+    """with gated() as g: ...; g.ran: {gate name: launches} of this feature's kernels that ran inside."""
+
+    def __enter__(self):
+        lib.vips_hip_gate_reset()
+        lib.vips_hip_gate_enable(1)
+        self.ran = None
+        return self
+
+    def __exit__(self, *exc):
+        try:
+            if exc[0] is None:
+                self.ran = {k: n for k, (n, _) in libvips_amd.gate_report().items()
+                            if k.startswith(("canvas_", "flatten_", "addalpha"))}
+        finally:
+            lib.vips_hip_gate_enable(0)
+            lib.vips_hip_gate_reset()
+        return False
+
+
+class general_kernel(object):
+    """The one-pel-a-lane kernel for everything inside (the library reads the variable at every dispatch)."""
+
+    def __init__(self, on=True):
+        self.on = on
+
+    def __enter__(self):
+        if self.on:
+            os.environ["VIPS_HIP_NO_CANVAS_STREAM"] = "1"
+
+    def __exit__(self, *exc):
+        os.environ.pop("VIPS_HIP_NO_CANVAS_STREAM", None)
+        return False
+
+
+def same(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape, want.dtype, want.shape)
+    assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), what
+
+
+def noise(w, h, dtype, bands, seed):
+    a = helpers.lcg_image(w, h, bands, dtype, seed)
+    return np.ascontiguousarray(a)
+
+
+def ink_of(background, bands, dtype):
+    """vips__vector_to_ink through the library (pinned to the reference in tests/test_canvas_host.py and, here, by
+    test_the_embed_model_is_the_reference)."""
+    bg = np.atleast_1d(np.asarray(background, np.float64))
+    out = np.zeros(bands, dtype)
+    _ffi.check(lib.vips_hip_vector_to_ink(bg.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(bg), bands,
+                                          helpers.DTYPE_FORMATS[np.dtype(dtype)], out.ctypes.data))
+    return out
+
+
+def white_ink(bands, dtype, interpretation):
+    """vips_region_paint of (int) max_alpha: a memset byte for integer formats, the value for float formats."""
+    white = int({25: 65535.0, 26: 65535.0, 28: 1.0}.get(interpretation, 255.0))
+    if np.dtype(dtype).kind == "f":
+        return np.full(bands, white, dtype)
+    return np.full(bands * np.dtype(dtype).itemsize, white & 0xff, np.uint8).view(dtype)
+
+
+def model_embed(src, x, y, cw, ch, extend, ink=None):
+    """vips_embed in numpy: src (h, w, b); ink the pel of black / white / background."""
+    h, w, b = src.shape
+    X, Y = np.arange(cw) - x, np.arange(ch) - y
+    if extend == "copy":
+        return np.ascontiguousarray(src[np.clip(Y, 0, h - 1)][:, np.clip(X, 0, w - 1)])
+    if extend == "repeat":
+        return np.ascontiguousarray(src[Y % h][:, X % w])
+    if extend == "mirror":
+        mx, my = X % (2 * w), Y % (2 * h)
+        return np.ascontiguousarray(src[np.where(my < h, my, 2 * h - 1 - my)][:, np.where(mx < w, mx, 2 * w - 1 - mx)])
+    out = np.empty((ch, cw, b), src.dtype)
+    out[:] = np.zeros(b, src.dtype) if ink is None else ink
+    xin, yin = (X >= 0) & (X < w), (Y >= 0) & (Y < h)
+    if xin.any() and yin.any():
+        out[np.ix_(yin, xin)] = src[Y[yin]][:, X[xin]]
+    return out
+
+
+def embed_args(x, y, w, h, extend=None, background=None):
+    s = "x=%d,y=%d,width=%d,height=%d" % (x, y, w, h)
+    if extend is not None:
+        s += ",extend=%s" % extend
+    if background is not None:
+        s += ",background=%s" % " ".join(repr(float(v)) for v in np.atleast_1d(background))
+    return s
+
+
+def ref_one(nick, src, args, interp=0):
+    """The reference's pixels and, where the input's tag can be handed to it, its interpretation.  (The shim takes an
+    interpretation of 0 to mean "derive one from the bands and the format", so MULTIBAND cannot be set through it: such
+    calls give the pixels alone, and test_the_headers_are_the_reference sets MULTIBAND through a .v file.)"""
+    if interp == 0:
+        return Ref.run(nick, src, args)
+    return Ref.run_interp(nick, src, args, interpretation=interp)
+
+
+def both(fn_dev, fn_ref, what):
+    """The library's result and the reference's: equal images, or both an error with the reference's words (what
+    follows its nickname) in the library's message.  fn_dev may return an Image and fn_ref (array, interpretation),
+    as Ref.run_interp does: the header's interpretation is then compared too."""
+    try:
+        want = fn_ref()
+    except RuntimeError as e:
+        words = str(e).strip().splitlines()[-1].split(": ")[-1]
+        with pytest.raises(VipsHipError) as info:
+            fn_dev()
+        assert words in str(info.value), (what, str(e), str(info.value))
+        return None
+    got = fn_dev()
+    if isinstance(got, Image):
+        if isinstance(want, tuple):
+            want, interpretation = want
+            assert lib.vips_hip_image_get_interpretation(got._h) == interpretation, (what, "interpretation")
+        assert (got.width, got.height, got.bands) == (want.shape[1], want.shape[0], want.shape[2]), (what, "header")
+        got = got.numpy()
+    same(got, want, what)
+    return got
+
+
+# ---------------------------------------------------------------- frames: windows of larger images
+
+def upload_frame(frame):
+    """A (rows, stride) uint8 array in HBM."""
+    return Image.new_from_array(np.ascontiguousarray(frame)[:, :, None])
+
+
+def embed_gen_in_frames(src, x, y, cw, ch, extend, ink, margin=4, in_window=None, out_rect=None):
+    """vips_hip_embed_gen with the input and the output as windows of larger frames whose rows start on dwords (margin
+    * pel a multiple of 4) or anywhere (margin 1 .. 3 with an odd pel); the output frame's bytes outside the window
+    must stay as they were.  in_window / out_rect: (left, top, width, height) of the image that the input frame
+    holds / of the canvas that is made."""
+    h, w, b = src.shape
+    pel = b * src.dtype.itemsize
+    il, it, iw, ih = in_window or (0, 0, w, h)
+    ol, ot, ow, oh = out_rect or (0, 0, cw, ch)
+    raw = np.ascontiguousarray(src[it:it + ih, il:il + iw]).view(np.uint8).reshape(ih, iw * pel)
+    istride = (margin * pel + iw * pel + 5 + 3) // 4 * 4
+    fin = np.full((ih + 2, istride), 0x3C, np.uint8)
+    fin[1:1 + ih, margin * pel:margin * pel + iw * pel] = raw
+    ostride = (margin * pel + ow * pel + 7 + 3) // 4 * 4
+    fout = np.full((oh + 2, ostride), SENTINEL, np.uint8)
+    din, dout = upload_frame(fin), upload_frame(fout)
+    fmt = helpers.DTYPE_FORMATS[src.dtype]
+    rin = _ffi.Region(din.data_ptr + istride + margin * pel, il, it, iw, ih, w, h, b, fmt, istride)
+    rout = _ffi.Region(dout.data_ptr + ostride + margin * pel, ol, ot, ow, oh, cw, ch, b, fmt, ostride)
+    inkb = np.zeros(32, np.uint8)
+    if ink is not None:
+        inkb[:pel] = np.ascontiguousarray(ink).view(np.uint8)
+    _ffi.check(lib.vips_hip_embed_gen(EXTENDS[extend], inkb.ctypes.data, x, y, ctypes.byref(rin), ctypes.byref(rout)))
+    back = dout.numpy()[:, :, 0]
+    got = back[1:1 + oh, margin * pel:margin * pel + ow * pel].copy()
+    back[1:1 + oh, margin * pel:margin * pel + ow * pel] = SENTINEL
+    assert (back == SENTINEL).all(), "bytes outside the output window were written"
+    return np.ascontiguousarray(got).view(src.dtype).reshape(oh, ow, b)
+
+
+def sweep_widths(pel):
+    """Canvas widths whose rows are 1, 15, 16, 17, 47, 48, 49 bytes (rounded up to whole pels) and one wave's worth of
+    the streaming kernel's groups - 1 / + 0 / + 1 pel."""
+    group = lib.vips_hip_canvas_step(1, pel) or 16
+    wave = 64 * group // pel if group % pel == 0 else 64
+    return sorted({-(-n // pel) for n in (1, 15, 16, 17, 47, 48, 49)} | {wave - 1, wave, wave + 1})
+
+
+def sweep_geometries(cw):
+    """(canvas height, image width, image height, x, y): a row of interior alone, read one pel in; borders all round;
+    the image clipped at the right, the top and the bottom; a canvas several periods wide and high round a small image
+    that sticks out at the left."""
+    small = max(1, cw // 3)
+    return [(1, cw + 2, 1, -1, 0),
+            (6, max(1, cw - 3), 4, min(2, cw - 1), 1),
+            (6, cw, 7, min(3, cw - 1), -1),
+            (6, small, 2, -(small // 2), 3)]
+
+
+# ---------------------------------------------------------------- the model is the reference
+
+@pytest.mark.parametrize("extend", sorted(EXTENDS))
+def test_the_embed_model_is_the_reference(extend):
+    for pel, seed in ((1, 3), (3, 5), (6, 7), (16, 9), (24, 11)):
+        dtype, bands = PELS[pel]
+        src = noise(7, 5, dtype, bands, seed)
+        background = [10, 200, 30, 77][:bands] if bands > 1 else 200
+        for interp in (0, 25, 28):
+            if extend != "white" and interp:
+                continue
+            ink = {"white": white_ink(bands, dtype, interp), "background": ink_of(background, bands, dtype)}.get(extend)
+            for x, y, cw, ch in ((2, 1, 12, 9), (-3, -2, 9, 6), (0, 0, 30, 23), (-2, -1, 3, 3), (5, 4, 14, 10), (6, 0, 9, 5)):
+                want = Ref.run("embed", src, embed_args(x, y, cw, ch, extend, background if extend == "background" else None),
+                               interpretation=interp)
+                same(model_embed(src, x, y, cw, ch, extend, ink), want, (extend, pel, interp, x, y, cw, ch))
+
+
+def test_anchors():
+    """A 4 x 3 one-band image of 1 .. 12: what the reference was seen to make of it."""
+    a = np.arange(1, 13, dtype=np.uint8).reshape(3, 4, 1)
+    im = Image.new_from_array(a)
+    assert im.embed(-2, -1, 3, 3).numpy()[:, :, 0].tolist() == [[7, 8, 0], [11, 12, 0], [0, 0, 0]]
+    assert im.embed(5, 4, 14, 10, extend="mirror").numpy()[0, :, 0].tolist() == [12, 12, 11, 10, 9, 9, 10, 11, 12, 12, 11, 10, 9, 9]
+    block = Image.new_from_array(np.full((2, 2, 1), 200, np.uint8))
+    got = im.insert(block, 3, 2, expand=True, background=9).numpy()
+    assert got.shape == (4, 5, 1) and got[3, :, 0].tolist() == [9, 9, 9, 200, 200]
+    for args in (embed_args(-2, -1, 3, 3), embed_args(5, 4, 14, 10, "mirror")):
+        kw = dict(kv.split("=") for kv in args.split(","))
+        same(im.embed(int(kw["x"]), int(kw["y"]), int(kw["width"]), int(kw["height"]), extend=kw.get("extend")).numpy(),
+             Ref.run("embed", a, args), args)
+
+
+# ---------------------------------------------------------------- embed: the two kernels against the model
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
+@pytest.mark.parametrize("pel", sorted(PELS))
+def test_embed_sweep(pel, kernel):
+    dtype, bands = PELS[pel]
+    streams = kernel == "stream" and lib.vips_hip_canvas_step(1, pel) != 0
+    background = ink_of([10, 200, 30, 77][:bands] if bands > 1 else 200, bands, dtype)
+    for cw in sweep_widths(pel):
+        for ch, iw, ih, x, y in sweep_geometries(cw):
+            src = noise(iw, ih, dtype, bands, 100 + cw)
+            for extend in sorted(EXTENDS):
+                ink = {"white": white_ink(bands, dtype, 0), "background": background}.get(extend)
+                with general_kernel(kernel == "general"), gated() as g:
+                    got = embed_gen_in_frames(src, x, y, cw, ch, extend, ink)
+                assert g.ran == {"canvas_stream" if streams else "canvas_general": 1}, (g.ran, pel, cw, extend)
+                same(got, model_embed(src, x, y, cw, ch, extend, ink), (kernel, pel, cw, ch, iw, ih, x, y, extend))
+
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
+@pytest.mark.parametrize("pel", [1, 2, 3, 6])
+def test_embed_interior_offsets(pel, kernel):
+    """x * pel = 0, 1, 2, 3 mod 4 and across a 16-byte group, an image that starts left of, on and right of the canvas
+    edge: the source group of an output group starts anywhere."""
+    dtype, bands = PELS[pel]
+    src = noise(90, 3, dtype, bands, 41)
+    for x in list(range(-19, 20)) + [33, 47, 48, 49]:
+        for extend in ("black", "mirror"):
+            with general_kernel(kernel == "general"), gated() as g:
+                got = embed_gen_in_frames(src, x, 1, 120, 5, extend, None)
+            assert g.ran == {"canvas_" + kernel: 1}, g.ran
+            same(got, model_embed(src, x, 1, 120, 5, extend), (kernel, pel, x, extend))
+
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
+def test_embed_tiny_images_and_many_periods(kernel):
+    """A 1 x 1 and a 1 x n image under repeat and mirror (periods 1 and 2), a canvas several periods wide and high."""
+    for pel in (1, 3, 4, 12):
+        dtype, bands = PELS[pel]
+        for iw, ih in ((1, 1), (1, 5), (5, 1), (2, 3)):
+            src = noise(iw, ih, dtype, bands, 51 + iw)
+            for x, y in ((0, 0), (-7, 4), (13, -9), (40, 40), (-100, -100)):
+                for extend in ("repeat", "mirror", "copy"):
+                    if extend == "copy" and (x >= 37 or y >= 11 or x + iw <= 0 or y + ih <= 0):
+                        continue
+                    with general_kernel(kernel == "general"), gated() as g:
+                        got = embed_gen_in_frames(src, x, y, 37, 11, extend, None)
+                    assert g.ran == {"canvas_" + kernel: 1}, g.ran
+                    same(got, model_embed(src, x, y, 37, 11, extend), (kernel, pel, iw, ih, x, y, extend))
+
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
+def test_embed_region_views(kernel):
+    """A rect of the canvas from a window of the image: what vips_hip_embed_need names is enough, less is refused, rows
+    that start off a dword take the one-pel-a-lane kernel."""
+    dtype, bands = PELS[3]
+    src = noise(40, 30, dtype, bands, 61)
+    x, y, cw, ch = 9, 7, 70, 50
+    for extend in sorted(EXTENDS):
+        ink = {"white": white_ink(bands, dtype, 0), "background": ink_of([1, 2, 3], bands, dtype)}.get(extend)
+        whole = model_embed(src, x, y, cw, ch, extend, ink)
+        for rect in ((0, 0, 70, 5), (0, 5, 70, 9), (3, 20, 50, 13), (0, 38, 70, 12), (60, 0, 10, 50)):
+            need = (ctypes.c_int * 4)()
+            lib.vips_hip_embed_need(EXTENDS[extend], 40, 30, x, y, rect[0], rect[1], rect[2], rect[3], need)
+            window = tuple(need) if need[2] and need[3] else (0, 0, 1, 1)
+            for margin in (4, 1):
+                with general_kernel(kernel == "general"), gated() as g:
+                    got = embed_gen_in_frames(src, x, y, cw, ch, extend, ink, margin=margin, in_window=window, out_rect=rect)
+                assert g.ran == {"canvas_stream" if kernel == "stream" and margin == 4 else "canvas_general": 1}, g.ran
+                same(got, whole[rect[1]:rect[1] + rect[3], rect[0]:rect[0] + rect[2]], (kernel, extend, rect, margin))
+            if need[3] > 1:
+                lib.vips_hip_error_clear()
+                with pytest.raises(VipsHipError, match="embed: input region too small"):
+                    embed_gen_in_frames(src, x, y, cw, ch, extend, ink, in_window=(need[0], need[1] + 1, need[2], need[3] - 1),
+                                        out_rect=rect)
+
+
+# ---------------------------------------------------------------- embed: build() against the reference
+
+def dev_embed(src, x, y, w, h, extend=None, background=None, interp=0):
+    return Image.new_from_array(src, interp).embed(x, y, w, h, extend=extend, background=background)
+
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
+@pytest.mark.parametrize("extend", sorted(EXTENDS))
+def test_embed_against_the_reference(extend, kernel):
+    """Offsets negative, zero and positive, the image clipped on each side, wholly outside (an error in four modes, a
+    result in repeat and mirror), the identity."""
+    for pel in (3, 4, 8):
+        dtype, bands = PELS[pel]
+        src = noise(12, 8, dtype, bands, 71)
+        for x, y, cw, ch in ((0, 0, 12, 8), (0, 0, 16, 8), (4, 3, 24, 16), (-5, 0, 12, 8), (7, 0, 12, 8), (0, -6, 12, 8),
+                             (0, 5, 12, 8), (-3, -2, 30, 20), (12, 0, 12, 8), (0, 8, 12, 8), (-12, 0, 12, 8), (40, 40, 9, 9),
+                             (-40, 3, 9, 9)):
+            args = embed_args(x, y, cw, ch, extend)
+            with general_kernel(kernel == "general"):
+                for interp in (INTERP["b-w"], INTERP["srgb"]):
+                    both(lambda: dev_embed(src, x, y, cw, ch, extend, interp=interp),
+                         lambda: ref_one("embed", src, args, interp), (pel, args, interp))
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.int32, np.float32, np.float64], ids=lambda d: np.dtype(d).name)
+def test_embed_white_and_background(dtype):
+    """What vips_region_paint writes into pels wider than a byte, and vips__vector_to_ink's casts; a vector of one
+    value, of one per band, of the wrong length; a background without an extend."""
+    src = noise(5, 4, dtype, 3, 81)
+    for interp in (0, INTERP["rgb16"], INTERP["scrgb"], INTERP["b-w"]):
+        args = embed_args(2, 1, 11, 7, "white")
+        both(lambda: dev_embed(src, 2, 1, 11, 7, "white", interp=interp),
+             lambda: ref_one("embed", src, args, interp), (args, interp))
+    for background in (7, [1.5, 300, -4], [70000.7, 2 ** 33, -2 ** 33], [1, 2], [1, 2, 3, 4]):
+        for extend in ("background", None, "black"):
+            args = embed_args(2, 1, 11, 7, extend, background)
+            both(lambda: dev_embed(src, 2, 1, 11, 7, extend, background), lambda: Ref.run("embed", src, args), args)
+    # the identity comes before the ink: no error
+    args = embed_args(0, 0, 5, 4, "background", [1, 2])
+    both(lambda: dev_embed(src, 0, 0, 5, 4, "background", [1, 2]), lambda: Ref.run("embed", src, args), args)
+    one = noise(5, 4, dtype, 1, 83)
+    args = embed_args(2, 1, 11, 7, "background", [9, 8, 7])
+    both(lambda: dev_embed(one, 2, 1, 11, 7, "background", [9, 8, 7]), lambda: Ref.run("embed", one, args), args)
+
+
+# ---------------------------------------------------------------- gravity
+
+DIRECTIONS = ["centre", "north", "east", "south", "west", "north-east", "south-east", "south-west", "north-west"]
+
+
+@pytest.mark.parametrize("direction", DIRECTIONS)
+def test_gravity(direction):
+    src = noise(9, 6, np.uint8, 4, 91)
+    im = Image.new_from_array(src, "srgb")
+    for w, h in ((14, 11), (15, 10), (9, 6), (20, 6), (6, 4)):  # odd and even slack, none, a canvas smaller than the image
+        for extend, background in ((None, None), ("mirror", None), (None, [1, 2, 3, 4]), ("white", None)):
+            args = "direction=%s,width=%d,height=%d" % (direction, w, h)
+            if extend:
+                args += ",extend=" + extend
+            if background:
+                args += ",background=" + " ".join(str(float(v)) for v in background)
+            both(lambda: im.gravity(direction, w, h, extend=extend, background=background),
+                 lambda: Ref.run_interp("gravity", src, args, interpretation=INTERP["srgb"]), args)
+
+
+# ---------------------------------------------------------------- flatten: whole domains
+
+def flatten_args(background=None, max_alpha=None):
+    parts = []
+    if background is not None:
+        parts.append("background=" + " ".join(repr(float(v)) for v in np.atleast_1d(background)))
+    if max_alpha is not None:
+        parts.append("max_alpha=%r" % float(max_alpha))
+    return ",".join(parts)
+
+
+def check_flatten(src, background=None, max_alpha=None, interp=0, family=None):
+    args = flatten_args(background, max_alpha)
+    with gated() as g:
+        got = both(lambda: Image.new_from_array(src, interp).flatten(background=background, max_alpha=max_alpha),
+                   lambda: ref_one("flatten", src, args, interp), (src.dtype, src.shape, args, interp))
+    if family and got is not None:
+        assert g.ran == {family: 1}, g.ran
+    return got
+
+
+@pytest.mark.parametrize("bands", [2, 4, 5])
+@pytest.mark.parametrize("background", [None, 1, 255, 128, [3, 200, 77, 9]], ids=str)
+def test_flatten_every_uchar_case(bands, background):
+    """The pel at (a, p) has value p and alpha a: every product the float tables can make; 4 bands take the reference's
+    loop of its own (and the four-pels-a-lane kernel), 2 and 5 the general one."""
+    if isinstance(background, list):
+        background = background[:bands - 1]
+    p, a = np.meshgrid(np.arange(256, dtype=np.uint8), np.arange(256, dtype=np.uint8))
+    colour = [p if z % 2 == 0 else (255 - p) for z in range(bands - 1)]
+    src = np.ascontiguousarray(np.dstack(colour + [a]))
+    check_flatten(src, background, family="flatten_u8")
+    check_flatten(src[:, :253], background, family="flatten_u8")  # a ragged end for the four-pels-a-lane kernel
+
+
+WIDE_P = [0, 1, 255, 256, 32767, 32768, 65534, 65535]
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32, np.float64], ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("background", [None, 1, 65535, [40000]], ids=str)
+def test_flatten_every_ushort_alpha(dtype, background):
+    """A 65536-wide image, alpha = the column, rows of eight values: the double macros on every alpha."""
+    a = np.arange(65536, dtype=np.uint16)
+    src = np.empty((len(WIDE_P), 65536, 2), np.uint16)
+    src[:, :, 1] = a
+    for r, p in enumerate(WIDE_P):
+        src[r, :, 0] = p
+    check_flatten(src.astype(dtype), background, interp=INTERP["grey16"], family="flatten_any")
+
+
+def test_flatten_paths():
+    """max_alpha below the format's maximum (through double and back) with alphas above it; max_alpha unset on rgb16 /
+    grey16; one band; five bands; every other format; a vector of the wrong length; a complex image."""
+    u16 = noise(33, 9, np.uint16, 4, 95)
+    check_flatten(u16, [1000, 2000, 3000], max_alpha=4095)
+    check_flatten(u16, None, max_alpha=4095)
+    u8 = noise(33, 9, np.uint8, 4, 96)
+    check_flatten(u8, [10, 20, 30], max_alpha=100)
+    check_flatten(u16, [1000, 2000, 3000], interp=INTERP["rgb16"], family="flatten_any")
+    check_flatten(u16[:, :, :2], 9, interp=INTERP["grey16"], family="flatten_any")
+    check_flatten(u16[:, :, :1], 9)
+    check_flatten(noise(33, 9, np.uint16, 5, 97), [1, 2, 3, 4], interp=INTERP["rgb16"], family="flatten_any")
+    for dtype in (np.int8, np.int16, np.uint32, np.int32, np.float32, np.float64):
+        src = noise(33, 9, dtype, 3, 98)
+        if np.dtype(dtype).kind != "f":
+            src[:, :, 2] = np.abs(src[:, :, 2].astype(np.int64)) % 256  # an alpha inside 0 .. max_alpha
+        else:
+            src[:, :, 2] = np.abs(src[:, :, 2]) % 256
+        check_flatten(src, [12, 200])
+        check_flatten(src, None)
+    check_flatten(u8, [1, 2])
+    check_flatten(u8, [0, 0])  # black comes before the vector's length
+    lib.vips_hip_error_clear()
+    with pytest.raises(VipsHipError, match="flatten: image must be non-complex"):
+        Image.new_from_array(np.ones((4, 4, 2), np.complex64)).flatten()
+    with pytest.raises(RuntimeError, match="flatten: image must be non-complex"):
+        Ref.run("flatten", np.ones((4, 4, 2), np.complex64))
+
+
+# ---------------------------------------------------------------- the headers
+
+@pytest.mark.parametrize("interp", ["srgb", "rgb16", "multiband"])
+def test_the_headers_are_the_reference(tmp_path, interp):
+    """Size, bands, format and interpretation of what the four one-image operations return, against the reference's
+    header: the identity embed (a copy), every extend, gravity, flatten on its table, double-macro, one-band-copy and
+    through-double paths, addalpha.  A wrong tag would change the default max_alpha of whatever comes next.  MULTIBAND
+    goes to the reference's command line in a .v file's header (the shim cannot set it)."""
+    code = INTERP[interp]
+
+    def ref(nick, array, args, positional=(), options=()):
+        if code:
+            return Ref.run_interp(nick, array, args, interpretation=code)
+        return ref_cli(tmp_path, nick, [(array, code)], positional, options)
+
+    for dtype in (np.uint8, np.uint16, np.float32):
+        src = noise(8, 6, dtype, 4, 141)
+        im = Image.new_from_array(src, interp)
+        for x, y, w, h, extend in [(0, 0, 8, 6, None)] + [(2, -1, 13, 9, e) for e in sorted(EXTENDS)]:
+            both(lambda: im.embed(x, y, w, h, extend=extend),
+                 lambda: ref("embed", src, embed_args(x, y, w, h, extend), [x, y, w, h], ["--extend", extend] if extend else []),
+                 ("embed", dtype, interp, x, y, w, h, extend))
+        both(lambda: im.gravity("south", 9, 11, extend="copy"),
+             lambda: ref("gravity", src, "direction=south,width=9,height=11,extend=copy", ["south", 9, 11], ["--extend", "copy"]),
+             ("gravity", dtype, interp))
+        one = Image.new_from_array(src[:, :, :1], interp)
+        for image, array, kw, args, options in (
+                (im, src, {}, "", []), (im, src, {"background": [1, 2, 3]}, "background=1 2 3", ["--background", "1 2 3"]),
+                (im, src, {"max_alpha": 100}, "max_alpha=100", ["--max-alpha", "100"]),  # through double for integers
+                (one, src[:, :, :1], {}, "", [])):                                         # a copy
+            both(lambda: image.flatten(**kw), lambda: ref("flatten", array, args, [], options),
+                 ("flatten", dtype, interp, args, array.shape))
+        both(lambda: im.addalpha(), lambda: ref("addalpha", src, ""), ("addalpha", dtype, interp))
+        both(lambda: one.addalpha(), lambda: ref("addalpha", src[:, :, :1], ""), ("addalpha of one band", dtype, interp))
+
+
+# ---------------------------------------------------------------- addalpha
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.int8, np.uint16, np.int16, np.uint32, np.int32, np.float32, np.float64],
+                         ids=lambda d: np.dtype(d).name)
+def test_addalpha(dtype):
+    for interp in ("srgb", "rgb16", "b-w"):
+        for bands in (1, 3):
+            src = noise(19, 7, dtype, bands, 99)
+            with gated() as g:
+                both(lambda: Image.new_from_array(src, interp).addalpha(),
+                     lambda: Ref.run_interp("addalpha", src, "", interpretation=INTERP[interp]), (dtype, interp, bands))
+            assert g.ran == {"addalpha": 1}, g.ran
+    # a transparent canvas and back: gravity onto the alpha's zero, flatten against black
+    src = noise(9, 5, np.uint8, 3, 101)
+    rgba = Image.new_from_array(src, "srgb").addalpha()
+    same(rgba.gravity("centre", 15, 9).flatten().numpy(), model_embed(src, 3, 2, 15, 9, "black"), "round trip")
+
+
+# ---------------------------------------------------------------- insert / join: the reference's command line
+
+def ref_cli(tmp_path, op, images, positional, options):
+    """-> (array, interpretation) of `vips <op> <images> out.v [options] -- <positional>`; RuntimeError with its words."""
+    paths = []
+    for i, (array, interp) in enumerate(images):
+        paths.append(str(tmp_path / ("in%d.v" % i)))
+        helpers.write_v(paths[-1], array, interp)
+    out = str(tmp_path / "out.v")
+    cmd = [VIPS, op] + paths + [out] + list(options) + ["--"] + [str(p) for p in positional]
+    r = subprocess.run(cmd, env=helpers.ref_cli_env(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(r.stderr.strip() or "vips %s failed" % op)
+    return helpers.read_v(out)
+
+
+def check_two(tmp_path, op, a, b, dev, positional, options, what):
+    (sa, ia), (sb, ib) = a, b
+    da, db = Image.new_from_array(sa, ia), Image.new_from_array(sb, ib)
+    interps = {}
+
+    def run_dev():
+        out = dev(da, db)
+        interps["dev"] = lib.vips_hip_image_get_interpretation(out._h)
+        return out.numpy()
+
+    def run_ref():
+        array, interps["ref"] = ref_cli(tmp_path, op, [a, b], positional, options)
+        return array
+
+    with gated() as g:
+        got = both(run_dev, run_ref, what)
+    if got is not None:
+        assert interps["dev"] == interps["ref"], (what, interps)
+        assert sum(g.ran.get(k, 0) for k in ("canvas_stream", "canvas_general")) == 1, g.ran
+    return got
+
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
+def test_insert_positions(tmp_path, kernel):
+    """sub inside, over each edge and wholly outside, with and without expand."""
+    main = (noise(16, 12, np.uint8, 4, 111), INTERP["srgb"])
+    sub = (noise(5, 4, np.uint8, 4, 113), INTERP["srgb"])
+    for x, y in ((3, 2), (-2, 3), (14, 3), (4, -3), (4, 10), (-2, -3), (30, 2), (-9, -9), (2, 40), (11, 8)):
+        for expand in (False, True):
+            options = ["--background", "9 8 7 6"] + (["--expand"] if expand else [])
+            with general_kernel(kernel == "general"):
+                check_two(tmp_path, "insert", main, sub, lambda m, s: m.insert(s, x, y, expand=expand, background=[9, 8, 7, 6]),
+                          [x, y], options, (x, y, expand))
+
+
+def test_insert_formats_and_bands(tmp_path):
+    """vips__formatalike and vips__bandalike: pairs that promote, one band against three, three against four."""
+    def im(dtype, bands, seed, interp):
+        return noise(9, 7, dtype, bands, seed), interp
+
+    srgb, bw, rgb16, multi = INTERP["srgb"], INTERP["b-w"], INTERP["rgb16"], 0
+    pairs = [(im(np.uint8, 3, 1, srgb), im(np.uint16, 3, 2, rgb16)), (im(np.uint16, 3, 3, rgb16), im(np.uint8, 3, 4, srgb)),
+             (im(np.int32, 1, 5, bw), im(np.float32, 1, 6, bw)), (im(np.float32, 2, 7, multi), im(np.float64, 2, 8, multi)),
+             (im(np.int8, 1, 9, bw), im(np.uint16, 1, 10, bw)), (im(np.uint8, 1, 11, bw), im(np.uint8, 3, 12, srgb)),
+             (im(np.uint8, 3, 13, srgb), im(np.uint8, 1, 14, bw)), (im(np.uint16, 1, 15, bw), im(np.float32, 3, 16, srgb)),
+             (im(np.uint8, 3, 17, srgb), im(np.uint8, 4, 18, srgb)), (im(np.uint8, 4, 19, srgb), im(np.uint8, 2, 20, multi))]
+    for a, b in pairs:
+        for background, option in ((None, []), ([300.5], ["--background", "300.5"])):
+            check_two(tmp_path, "insert", a, b, lambda m, s: m.insert(s, 4, -2, expand=True, background=background),
+                      [4, -2], ["--expand"] + option, (a[0].dtype, a[0].shape, b[0].dtype, b[0].shape, background))
+    a, b = pairs[0]
+    check_two(tmp_path, "insert", a, b, lambda m, s: m.insert(s, 1, 1, background=[1, 2]), [1, 1], ["--background", "1 2"],
+              "a vector of the wrong length")
+
+
+@pytest.mark.parametrize("direction", ["horizontal", "vertical"])
+@pytest.mark.parametrize("align", ["low", "centre", "high"])
+def test_join(tmp_path, direction, align):
+    a = (noise(11, 8, np.uint8, 3, 121), INTERP["srgb"])
+    for b in ((noise(6, 13, np.uint8, 3, 123), INTERP["srgb"]), (noise(17, 5, np.uint16, 1, 125), INTERP["grey16"])):
+        for shim in (0, 3):
+            for expand in (False, True):
+                options = ["--shim", str(shim), "--align", align, "--background", "50"] + (["--expand"] if expand else [])
+                check_two(tmp_path, "join", a, b,
+                          lambda p, q: p.join(q, direction, expand=expand, shim=shim, background=50, align=align),
+                          [direction], options, (direction, align, b[0].shape, shim, expand))
+
+
+# ---------------------------------------------------------------- the libvips module
+
+# (on host fibers the library under test is not the one the module was linked against)
+needs_module = pytest.mark.skipif(not helpers.have_module() or bool(os.environ.get("VIPS_HIP_LIBRARY")),
+                                  reason="host/_build missing, or another build of the library is under test")
+
+
+@needs_module
+@pytest.mark.parametrize("strips", [False, True], ids=["whole", "strips"])
+def test_module_canvas_classes(strips):
+    """embed_hip, gravity_hip, flatten_hip and addalpha_hip make the built-in operations' pixels, whole and strip by
+    strip (a small $VIPS_HIP_BUDGET, as tests/test_module.py): a mirror and a repeat embed whose border strips reach
+    back across the image, strips of nothing but ink, a background without an extend."""
+    Ref.load_module()
+    module = ctypes.CDLL(helpers.MODULE_LIB)
+    height = 700 if strips else 50
+    src = helpers.lcg_image(400, height, 4, np.uint8, 131)
+    cases = [("embed", embed_args(-10, height // 3, 420, 2 * height + 40, "mirror")),
+             ("embed", embed_args(7, -height // 2, 410, 2 * height, "repeat")),
+             ("embed", embed_args(3, 60, 440, height + 200, "copy")),
+             ("embed", embed_args(3, 60, 440, height + 200, None, [1, 2, 3, 4])),
+             ("embed", embed_args(0, 2 * height - 9, 401, 3 * height, "white")),
+             ("embed", embed_args(0, 0, 400, height)),
+             ("gravity", "direction=south-east,width=437,height=%d,extend=black" % (height + 111)),
+             ("gravity", "direction=centre,width=399,height=%d,extend=mirror" % (2 * height + 1)),
+             ("flatten", ""), ("flatten", "background=255 0 128"), ("flatten", "background=9,max_alpha=100"),
+             ("addalpha", "")]
+    if strips:
+        os.environ["VIPS_HIP_BUDGET"] = "300k"
+    before = module.vips_hip_module_strips_done()
+    try:
+        for nick, args in cases:
+            same(Ref.run(nick + "_hip", src, args, interpretation=INTERP["srgb"]),
+                 Ref.run(nick, src, args, interpretation=INTERP["srgb"]), "%s_hip %s" % (nick, args))
+    finally:
+        if strips:
+            del os.environ["VIPS_HIP_BUDGET"]
+    if strips:
+        assert module.vips_hip_module_strips_done() - before >= 4 * len(cases), "not strip-mined"
+
+
+@needs_module
+def test_module_errors_and_the_cases_of_the_original():
+    Ref.load_module()
+    src = noise(40, 30, np.uint8, 3, 133)
+    with pytest.raises(RuntimeError, match="embed_hip: bad dimensions"):
+        Ref.run("embed_hip", src, embed_args(40, 0, 10, 10))
+    with pytest.raises(RuntimeError, match="linear: vector must have 1 or 3 elements"):
+        Ref.run("embed_hip", src, embed_args(1, 1, 50, 50, "background", [1, 2]))
+    with pytest.raises(RuntimeError, match="linear: vector must have 1 or 2 elements"):
+        Ref.run("flatten_hip", src, "background=1 2 3")
+    # complex images, and pels wider than the kernels' ink, are the original's
+    z = (noise(9, 7, np.float32, 2, 135) + 1j * noise(9, 7, np.float32, 2, 137)).astype(np.complex64)
+    wide = noise(9, 7, np.float64, 5, 139)
+    for im in (z, wide):
+        args = embed_args(2, 1, 14, 11, "mirror")
+        same(Ref.run("embed_hip", im, args), Ref.run("embed", im, args), "embed_hip of %s" % im.dtype)
+        same(Ref.run("addalpha_hip", im, ""), Ref.run("addalpha", im, ""), "addalpha_hip of %s" % im.dtype)
+    with pytest.raises(RuntimeError, match="image must be non-complex"):
+        Ref.run("flatten_hip", z, "")
