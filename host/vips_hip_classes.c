@@ -2602,3 +2602,181 @@ static void
 vips_addalpha_hip_init(VipsAddAlphaHip *addalpha)
 {
 }
+
+/* linear_hip / invert_hip / abs_hip: arithmetic/linear.c:430-470, invert.c:171-183, abs.c:193-206.  Pointwise: an image
+ * over the HBM budget goes through in row strips of the same rows, each strip one call of the region form
+ * (vips_hip_linear_gen, vips_hip_invert_gen, vips_hip_abs_gen) straight into the strip's output.  The output's bands
+ * and format are the original's (a one-band image against n-element vectors makes n bands; abs of an unsigned image
+ * is a copy, which the region form makes too).  Complex images are the original's (hip_wants_original). */
+typedef struct _VipsLinearHip {
+	VipsHipOp parent_instance;
+	VipsArrayDouble *a;
+	VipsArrayDouble *b;
+	gboolean uchar;
+} VipsLinearHip;
+
+static int
+linear_hip_arguments(VipsHipOp *op, VipsHipLinear *l)
+{
+	VipsLinearHip *linear = (VipsLinearHip *) op;
+	VipsArrayDouble *vector[2] = { linear->a, linear->b };
+
+	vips_hip_linear_defaults(l);
+	for (int i = 0; i < 2; i++) {
+		int n;
+		const double *v;
+
+		if (!vector[i])
+			continue;
+		v = vips_array_double_get(vector[i], &n);
+		if (n < 1 || n > VIPS_HIP_ARITH_MAX_VECTOR) {
+			vips_error("linear_hip", "%s", "vector too long");
+			return -1;
+		}
+		if (i == 0) {
+			l->n_a = n;
+			memcpy(l->a, v, n * sizeof(double));
+		}
+		else {
+			l->n_b = n;
+			memcpy(l->b, v, n * sizeof(double));
+		}
+	}
+	l->uchar = linear->uchar;
+
+	return 0;
+}
+
+static int
+vips_linear_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsHipLinear l;
+
+	if (linear_hip_arguments(op, &l))
+		return -1;
+
+	return vips_hip_linear(in, out, &l);
+}
+
+static void
+vips_linear_hip_strip_close(VipsHipOp *op, void *plan)
+{
+	g_free(plan);
+}
+
+static int
+vips_linear_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	VipsHipLinear *l = g_new0(VipsHipLinear, 1);
+
+	if (linear_hip_arguments(op, l)) {
+		g_free(l);
+		return -1;
+	}
+	*plan = l;
+
+	return 0;
+}
+
+static void
+vips_linear_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	*in_top = out_top;
+	*in_rows = out_rows;
+}
+
+static int
+vips_linear_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_linear_gen((const VipsHipLinear *) plan, in, out);
+}
+
+HIP_SUBCLASS_FULL(VipsLinearHip, vips_linear_hip, "linear_hip", "calculate (a * in + b) (MI355X)", HIP_STRIPS(vips_linear_hip))
+
+static void
+vips_linear_hip_args(VipsLinearHipClass *class)
+{
+	VIPS_ARG_BOXED(class, "a", 110, "a", "Multiply by this",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLinearHip, a), VIPS_TYPE_ARRAY_DOUBLE);
+	VIPS_ARG_BOXED(class, "b", 111, "b", "Add this",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLinearHip, b), VIPS_TYPE_ARRAY_DOUBLE);
+	VIPS_ARG_BOOL(class, "uchar", 112, "uchar", "Output should be uchar",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsLinearHip, uchar), FALSE);
+}
+
+static void
+vips_linear_hip_init(VipsLinearHip *linear)
+{
+}
+
+typedef struct _VipsInvertHip {
+	VipsHipOp parent_instance;
+} VipsInvertHip;
+
+typedef VipsInvertHip VipsAbsHip;
+
+static int
+vips_invert_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_invert(in, out);
+}
+
+static int
+vips_abs_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_abs(in, out);
+}
+
+/* (no plan: the region forms take nothing but the regions) */
+static int
+vips_invert_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	*plan = NULL;
+
+	return 0;
+}
+
+static void
+vips_invert_hip_strip_close(VipsHipOp *op, void *plan)
+{
+}
+
+static int
+vips_invert_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_invert_gen(in, out);
+}
+
+static int
+vips_abs_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_abs_gen(in, out);
+}
+
+#define vips_invert_hip_strip_need vips_linear_hip_strip_need
+#define vips_abs_hip_strip_open vips_invert_hip_strip_open
+#define vips_abs_hip_strip_need vips_linear_hip_strip_need
+#define vips_abs_hip_strip_close vips_invert_hip_strip_close
+
+HIP_SUBCLASS_FULL(VipsInvertHip, vips_invert_hip, "invert_hip", "invert an image (MI355X)", HIP_STRIPS(vips_invert_hip))
+HIP_SUBCLASS_FULL(VipsAbsHip, vips_abs_hip, "abs_hip", "absolute value of an image (MI355X)", HIP_STRIPS(vips_abs_hip))
+
+static void
+vips_invert_hip_args(VipsInvertHipClass *class)
+{
+}
+
+static void
+vips_invert_hip_init(VipsInvertHip *invert)
+{
+}
+
+static void
+vips_abs_hip_args(VipsAbsHipClass *class)
+{
+}
+
+static void
+vips_abs_hip_init(VipsAbsHip *abs)
+{
+}

@@ -1556,7 +1556,8 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *   - affine / similarity / rotate of double images, with an interpolator other than nearest, bilinear and bicubic
  *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands;
  *   - embed / gravity of pels of more than 32 bytes (the canvas kernels' ink), flatten to a background of more than
- *     256 bytes.
+ *     256 bytes;
+ *   - linear with a vector of more than VIPS_HIP_ARITH_MAX_VECTOR elements (what the kernels keep in LDS).
  */
 static gboolean
 hip_wants_original(VipsHipOp *op, VipsImage *in)
@@ -1614,6 +1615,19 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 	if (strcmp(nick, "flatten_hip") == 0 && in->Bands > 1 &&
 		(guint64) (in->Bands - 1) * VIPS_MAX(VIPS_IMAGE_SIZEOF_ELEMENT(in), sizeof(double)) > 256)
 		return TRUE;
+	if (strcmp(nick, "linear_hip") == 0) {
+		VipsArrayDouble *vector[2] = { NULL, NULL };
+		gboolean longer = FALSE;
+
+		g_object_get(op, "a", &vector[0], "b", &vector[1], NULL);
+		for (int i = 0; i < 2; i++)
+			if (vector[i]) {
+				longer |= VIPS_AREA(vector[i])->n > VIPS_HIP_ARITH_MAX_VECTOR;
+				vips_area_unref(VIPS_AREA(vector[i]));
+			}
+		if (longer)
+			return TRUE;
+	}
 	if (strcmp(nick, "thumbnail_image_hip") == 0) {
 		gboolean linear = FALSE;
 		int crop = 0;
@@ -1794,6 +1808,9 @@ g_module_check_init(GModule *module)
 	vips_gravity_hip_get_type();
 	vips_flatten_hip_get_type();
 	vips_addalpha_hip_get_type();
+	vips_linear_hip_get_type();
+	vips_invert_hip_get_type();
+	vips_abs_hip_get_type();
 
 	/* types registered by a module must never be unloaded */
 	g_module_make_resident(module);

@@ -1139,6 +1139,97 @@ VIPS_HIP_API int vips_hip_join(VipsHipImage *in1, VipsHipImage *in2, VipsHipImag
  * (0: that pel size takes the one-pel-a-lane kernel), for tests that want sizes round them. */
 VIPS_HIP_API int vips_hip_canvas_step(int what, int pel_size);
 
+/* ------------------------------------------------ arithmetic: linear / invert / abs, add / subtract / multiply / divide,
+ * stats / avg / deviate / min / max
+ *
+ * The pointwise operations of arithmetic/ (linear.c, invert.c, abs.c, add.c, subtract.c, multiply.c, divide.c) on any
+ * non-complex format, ONE launch an operation (arith.hip), bit for bit the reference's arithmetic: multiplies and adds
+ * separate, float division correctly rounded.  vips_stats and its single-number siblings (stats.c, avg.c, deviate.c,
+ * min.c, max.c) in one read-only pass for uchar, char, ushort, short and float images.  Complex images are refused with
+ * vips_check_noncomplex's words.  Results carry no orientation.
+ */
+#define VIPS_HIP_ARITH_MAX_VECTOR 32
+
+/* The arguments of vips_linear: out = in * a + b, @a and @b vectors of 1 or `bands` elements (a one-band image against
+ * n elements makes n bands, linear.c:131-145); @uchar: uchar output.  vips_hip_linear_defaults(): a = 1, b = 0. */
+typedef struct {
+	int n_a;
+	double a[VIPS_HIP_ARITH_MAX_VECTOR];
+	int n_b;
+	double b[VIPS_HIP_ARITH_MAX_VECTOR];
+	int uchar;
+} VipsHipLinear;
+VIPS_HIP_API void vips_hip_linear_defaults(VipsHipLinear *args);
+
+/* VipsHipArith: the operations vips_hip_arith_format and vips_hip_binary_plan know */
+typedef enum {
+	VIPS_HIP_ARITH_LINEAR = 0,
+	VIPS_HIP_ARITH_INVERT,
+	VIPS_HIP_ARITH_ABS,
+	VIPS_HIP_ARITH_ADD,
+	VIPS_HIP_ARITH_SUBTRACT,
+	VIPS_HIP_ARITH_MULTIPLY,
+	VIPS_HIP_ARITH_DIVIDE,
+	VIPS_HIP_ARITH_LAST
+} VipsHipArith;
+
+/* The operation's format table (linear.c:425-428, invert.c:166-169, abs.c:188-191, add.c:180-183, subtract.c:176-179,
+ * multiply.c:197-200, divide.c:199-202): the output format for an input (for two images: common) format; -1 for a
+ * complex or unknown format or operation.  Host only. */
+VIPS_HIP_API int vips_hip_arith_format(int op, int format);
+/* vips_linear_build restated (linear.c:121-209): the output's bands and format, whether the reference takes its
+ * single-element loops (every element of a and of b equal), and a_ready / b_ready (VIPS_HIP_ARITH_MAX_VECTOR doubles each,
+ * either may be NULL).  Errors in the reference's words: "linear: vector must have 1 or N elements".  Host only. */
+VIPS_HIP_API int vips_hip_linear_plan(const VipsHipLinear *args, int bands, int format, int *out_bands, int *out_format,
+	int *single, double *a_ready, double *b_ready);
+/* vips_arithmetic_build's three steps for two images (arithmetic.c:436-505): *@format the common format of
+ * vips__formatalike (arithmetic.c:76-109), *@out_format the operation's table applied to it, *@bands and
+ * *@interpretation by vips__bandalike (one band against n only: "<nickname>: not one band or N bands" otherwise; the
+ * interpretation of the image with the most bands, the left one's when they tie), *@width and *@height by
+ * vips__sizealike (the larger of each).  Host only. */
+VIPS_HIP_API int vips_hip_binary_plan(int op, int left_width, int left_height, int left_bands, int left_format,
+	int left_interpretation, int right_width, int right_height, int right_bands, int right_format,
+	int right_interpretation, int *format, int *out_format, int *bands, int *interpretation, int *width, int *height);
+/* stats.c:133-171 on a (bands + 1) x 10 matrix whose rows 1 .. bands hold min, max, sum, sum2 and the positions: row 0
+ * merged from them, then avg and sd of every row, in the reference's double expressions and order.  Host only. */
+VIPS_HIP_API int vips_hip_stats_finish(double *matrix, int bands, long long pels);
+
+/* The generate functions on a pair of windows of the same size.  linear: @out has the bands and format
+ * vips_hip_linear_plan gives for @in's; invert, abs: the same bands and format.  Bytes of @out's frame outside the
+ * window are not touched.  Where `data` and strides are multiples of 4 on both sides the streaming kernel runs,
+ * otherwise (and under VIPS_HIP_NO_ARITH_STREAM) the one-element-a-lane kernel. */
+VIPS_HIP_API int vips_hip_linear_gen(const VipsHipLinear *args, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_invert_gen(const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_abs_gen(const VipsHipRegion *in, const VipsHipRegion *out);
+
+/* Whole images.  @args NULL: the defaults.  abs of an unsigned image is a copy (abs.c:88-90). */
+VIPS_HIP_API int vips_hip_linear(VipsHipImage *in, VipsHipImage **out, const VipsHipLinear *args);
+VIPS_HIP_API int vips_hip_invert(VipsHipImage *in, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_abs(VipsHipImage *in, VipsHipImage **out);
+/* Two images: an operand whose format is not the common one goes through vips_hip_cast first; then ONE launch, which
+ * indexes a one-band operand by pel and reads zero outside an operand's own rectangle (no bandjoin or embed is made).
+ * divide gives 0 where the divisor is 0 (divide.c:130). */
+VIPS_HIP_API int vips_hip_add(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_subtract(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_multiply(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_divide(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+
+/* vips_stats: @out takes (bands + 1) * 10 doubles, row 0 over all bands, columns min, max, sum, sum2, avg, sd, xmin,
+ * ymin, xmax, ymax (stats.c:91-103).  uchar, char, ushort, short and float images (the square of a 32-bit value does not
+ * fit the 64-bit accumulator).  Integer sums are exact 64-bit integers converted once; float sums are doubles added in an
+ * order the image's geometry fixes.  NaN enters the sums and neither extreme.  Of equal extremes the first in raster
+ * order is reported. */
+VIPS_HIP_API int vips_hip_stats(VipsHipImage *in, double *out);
+/* avg.c:103-105, deviate.c:114-122, min.c / max.c without `size` and the position arrays: row 0 of the matrix. */
+VIPS_HIP_API int vips_hip_avg(VipsHipImage *in, double *out);
+VIPS_HIP_API int vips_hip_deviate(VipsHipImage *in, double *out);
+VIPS_HIP_API int vips_hip_min(VipsHipImage *in, double *out, int *x, int *y);
+VIPS_HIP_API int vips_hip_max(VipsHipImage *in, double *out, int *x, int *y);
+/* 0: the threads of a block of the arithmetic kernels; 1: the bytes of a group of the streaming kernels (of the output
+ * for the pointwise kernels, of one band's share of the input for stats); 2 / 3: the most blocks a pointwise / a stats
+ * launch has -- for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_arith_step(int what);
+
 #ifdef __cplusplus
 }
 #endif

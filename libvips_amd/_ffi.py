@@ -122,6 +122,19 @@ class Insert(ctypes.Structure):
     ]
 
 
+class Linear(ctypes.Structure):
+    """VipsHipLinear (include/vips_hip.h): the arguments of vips_linear."""
+
+    MAX_VECTOR = 32
+    _fields_ = [
+        ("n_a", ctypes.c_int),
+        ("a", ctypes.c_double * 32),
+        ("n_b", ctypes.c_int),
+        ("b", ctypes.c_double * 32),
+        ("uchar", ctypes.c_int),
+    ]
+
+
 def _load():
     # PyTorch-ROCm carries its own HIP runtime (soname libamdhip64.so).  Import it first so
     # libvipship.so, which needs that soname, binds to the SAME runtime: device pointers,
@@ -387,6 +400,29 @@ _SIGNATURES = {
     "vips_hip_insert": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, c_int, P(Insert)]),
     "vips_hip_join": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, P(Insert)]),
     "vips_hip_canvas_step": (c_int, [c_int, c_int]),
+    # linear / invert / abs, add / subtract / multiply / divide, stats / avg / deviate / min / max
+    "vips_hip_linear_defaults": (None, [P(Linear)]),
+    "vips_hip_arith_format": (c_int, [c_int, c_int]),
+    "vips_hip_linear_plan": (c_int, [P(Linear), c_int, c_int, P(c_int), P(c_int), P(c_int), P(c_double), P(c_double)]),
+    "vips_hip_binary_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                     P(c_int), P(c_int), P(c_int), P(c_int), P(c_int), P(c_int)]),
+    "vips_hip_stats_finish": (c_int, [P(c_double), c_int, ctypes.c_longlong]),
+    "vips_hip_linear_gen": (c_int, [P(Linear), RegionP, RegionP]),
+    "vips_hip_invert_gen": (c_int, [RegionP, RegionP]),
+    "vips_hip_abs_gen": (c_int, [RegionP, RegionP]),
+    "vips_hip_linear": (c_int, [c_void_p, P(c_void_p), P(Linear)]),
+    "vips_hip_invert": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_abs": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_add": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_subtract": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_multiply": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_divide": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_stats": (c_int, [c_void_p, P(c_double)]),
+    "vips_hip_avg": (c_int, [c_void_p, P(c_double)]),
+    "vips_hip_deviate": (c_int, [c_void_p, P(c_double)]),
+    "vips_hip_min": (c_int, [c_void_p, P(c_double), P(c_int), P(c_int)]),
+    "vips_hip_max": (c_int, [c_void_p, P(c_double), P(c_int), P(c_int)]),
+    "vips_hip_arith_step": (c_int, [c_int]),
 }
 
 MISSING = []

@@ -1,0 +1,736 @@
+// vips_linear, vips_invert, vips_abs (arithmetic/linear.c, invert.c, abs.c), vips_add, vips_subtract, vips_multiply,
+// vips_divide (add.c, subtract.c, multiply.c, divide.c) and the scan of vips_stats (stats.c) on the device (gfx950).
+//
+// The pointwise operations are ONE launch that writes every output byte once:
+//
+//   arith_stream<OP, IN, OUT>   lanes on consecutive 16-byte groups of an OUTPUT row: 16 / sizeof(OUT) elements, whose
+//                               operands are 16 * sizeof(IN) / sizeof(OUT) bytes of the input row -- 4 to 128, always
+//                               whole dwords at a dword offset, so with rows that start on dwords on every side the lane
+//                               loads them as aligned dwords (global_load_dwordx4 where there are four) and stores one
+//                               global_store_dwordx4.  The rows' groups are dealt to the lanes as one sequence; a row's
+//                               ragged last group goes element by element inside the same launch.  The constants of
+//                               vips_linear's band vectors lie in LDS and are picked by (element index) mod bands.
+//   arith_general<OP, IN, OUT>  one element a lane: defines correctness and takes what the stream declines -- rows that
+//                               do not start on dwords, a one-band operand against n bands (indexed by pel), operands
+//                               of different sizes (zero outside an operand's rectangle: vips__sizealike's black embed
+//                               at (0, 0), arithmetic.c:139-171) -- and everything under VIPS_HIP_NO_ARITH_STREAM.
+//
+// The arithmetic is the reference's, expression by expression (arith_elem below cites each); the file is compiled with
+// -ffp-contract=off, so multiplies and adds stay separate as in the reference's baseline x86-64 code, and float
+// division is the correctly rounded quotient (__fdiv_rn / __ddiv_rn).
+//
+// vips_stats: one read-only pass.
+//
+//   stats_stream<T, B>   B = 1 .. 4 bands, rows that start on dwords.  A lane takes 16 / sizeof(T) pels at a time -- B
+//                        groups of 16 bytes, so the band of every element of what it holds is known when the kernel is
+//                        compiled and the per-band accumulators stay in registers -- grid-strided over the image's
+//                        groups with a capped grid.  Per band: sum and sum of squares (64-bit integers for the integer
+//                        formats: exact; doubles for float), the extremes and the raster index of the FIRST pel that
+//                        holds each.  NaN never compares, so it enters neither extreme (stats.c:268-277) but does enter
+//                        the sums.  Lanes meet in LDS in a tree of fixed shape, thread 0 writes the block's partial to
+//                        a slab, the host merges the slab in index order: no floating atomics, the order depends on
+//                        the image's geometry alone.
+//   stats_general<T>     any band count and any row start: block (x, band), one element a lane and step.
+#include "gcn.h"
+#include "internal.h"
+#include "kernel_stmt.h"
+
+#include <cstdint>
+#include <cstdlib>
+#include <type_traits>
+
+namespace vh {
+
+constexpr int ARITH_THREADS = 256;
+constexpr int ARITH_GROUP = 16;            // bytes of the output a lane makes at a time
+constexpr int ARITH_GRID_BLOCKS = 256 * 8; // of a stream launch (as canvas_stream)
+constexpr int STATS_GRID_BLOCKS = 1024;    // four a CU, as hist_rects
+
+// ---------------------------------------------------------------- the reference's expressions
+
+// VIPS_FCLIP(0, t, 255) = fmax(0, fmin(255, t)) and the conversion to uchar (linear.c:277, :292): fmin gives 255 for a
+// NaN, as this comparison does; what is left lies in 0 .. 255 and the conversion truncates
+template <typename F>
+VH_DEV unsigned char arith_clip_u8(F t)
+{
+	F c = t < (F) 255 ? t : (F) 255;
+	c = c > (F) 0 ? c : (F) 0;
+	return (unsigned char) cvt_i32(c);
+}
+
+template <typename T>
+VH_DEV T arith_negate(T x)
+{
+	if constexpr (std::is_floating_point<T>::value)
+		return -x;
+	else
+		return (T) (0u - (unsigned int) x); // (wraps, as the reference's stores do)
+}
+
+// One output element.  x, y: the operands; (a1, b1) vips_linear's constants as floats for its single-element loops,
+// (ak, bk) element k of a_ready / b_ready.
+template <int OP, typename IN, typename OUT>
+VH_DEV OUT arith_elem(IN x, IN y, bool single, float a1, float b1, double ak, double bk)
+{
+	constexpr bool in_float = std::is_floating_point<IN>::value;
+	if constexpr (OP == ARITH_LINEAR) {
+		if constexpr (std::is_same<OUT, unsigned char>::value) {
+			if (single) {
+				// LOOP1uc, linear.c:266-279: float a1, b1; float t = a1 * p[x] + b1 -- for a double image the
+				// product and the sum are double (the usual conversions) and t rounds them
+				if constexpr (std::is_same<IN, double>::value)
+					return arith_clip_u8<float>((float) ((double) a1 * x + (double) b1));
+				else
+					return arith_clip_u8<float>(a1 * (float) x + b1);
+			}
+			// LOOPNuc, linear.c:283-294: double t = a[k] * p[i] + b[k]
+			return arith_clip_u8<double>(ak * (double) x + bk);
+		}
+		else if constexpr (std::is_same<OUT, float>::value) {
+			// LOOP1, linear.c:213-223: OUT a1 = a[0]; q = a1 * (OUT) p + b1, float arithmetic
+			if (single)
+				return a1 * (float) x + b1;
+			// LOOPN, linear.c:227-235: a[k] * (OUT) p[i] + b[k] -- the pel rounded to float, the arithmetic double,
+			// the store rounds
+			return (float) (ak * (double) (float) x + bk);
+		}
+		else
+			return ak * (double) x + bk; // LOOP1 and LOOPN of a double image are the same double expression
+	}
+	else if constexpr (OP == ARITH_INVERT) {
+		// invert.c:71-87: L - p for the unsigned formats, -1 * p for the others (an exact sign change for every
+		// number)
+		if constexpr (std::is_unsigned<IN>::value)
+			return (OUT) ((IN) ~(IN) 0 - x);
+		else
+			return arith_negate(x);
+	}
+	else if constexpr (OP == ARITH_ABS) {
+		// abs.c:100-120: p < 0 ? 0 - p : p; fabs(); the unsigned formats are a copy (abs.c:88-90)
+		if constexpr (std::is_same<IN, float>::value)
+			return __builtin_fabsf(x);
+		else if constexpr (std::is_same<IN, double>::value)
+			return __builtin_fabs(x);
+		else if constexpr (std::is_unsigned<IN>::value)
+			return x;
+		else
+			return x < 0 ? arith_negate(x) : x;
+	}
+	else if constexpr (OP == ARITH_DIVIDE) {
+		// divide.c:122-131: right == 0 ? 0 : (OUT) left / (OUT) right
+		if constexpr (std::is_same<OUT, double>::value)
+			return y == (IN) 0 ? 0.0 : __ddiv_rn((double) x, (double) y);
+		else
+			return y == (IN) 0 ? 0.0f : __fdiv_rn((float) x, (float) y);
+	}
+	else if constexpr (in_float) {
+		return OP == ARITH_ADD ? x + y : OP == ARITH_SUBTRACT ? x - y : x * y;
+	}
+	else {
+		// add.c:70-92, subtract.c:70-92, multiply.c:102-126: the sum, difference or product of the two values in a
+		// type that holds it (int64 for int images), stored to OUT; modulo 2^32 that is this
+		const unsigned int l = (unsigned int) x, r = (unsigned int) y;
+		return (OUT) (OP == ARITH_ADD ? l + r : OP == ARITH_SUBTRACT ? l - r : l * r);
+	}
+}
+
+// ---------------------------------------------------------------- registers <-> elements
+
+// element i (a constant once the loops are unrolled) of the dwords of a group
+template <typename T, int ND>
+VH_DEV T arith_take(const unsigned int (&d)[ND], int i)
+{
+	if constexpr (sizeof(T) == 1)
+		return (T) (d[i >> 2] >> (8 * (i & 3)));
+	else if constexpr (sizeof(T) == 2)
+		return (T) (d[i >> 1] >> (16 * (i & 1)));
+	else if constexpr (sizeof(T) == 4)
+		return __builtin_bit_cast(T, d[i]);
+	else
+		return __builtin_bit_cast(T, (unsigned long long) d[2 * i] | ((unsigned long long) d[2 * i + 1] << 32));
+}
+
+template <typename T>
+VH_DEV void arith_put(unsigned int (&w)[4], int i, T v)
+{
+	if constexpr (sizeof(T) == 1)
+		w[i >> 2] |= (unsigned int) (unsigned char) v << (8 * (i & 3));
+	else if constexpr (sizeof(T) == 2)
+		w[i >> 1] |= (unsigned int) (unsigned short) v << (16 * (i & 1));
+	else if constexpr (sizeof(T) == 4)
+		w[i] = __builtin_bit_cast(unsigned int, v);
+	else {
+		const unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
+		w[2 * i] = (unsigned int) bits;
+		w[2 * i + 1] = (unsigned int) (bits >> 32);
+	}
+}
+
+// ND dwords (1, 2 or a multiple of 4) at a dword-aligned offset
+template <int ND>
+VH_DEV void arith_load(gptr_in base, unsigned int off, unsigned int (&d)[ND])
+{
+	if constexpr (ND < 4)
+		gload_dwords<ND>(base, off, d);
+	else {
+#pragma unroll
+		for (int q = 0; q < ND / 4; q++) {
+			unsigned int t[4];
+			gload128(base, off + 16u * (unsigned int) q, t);
+#pragma unroll
+			for (int i = 0; i < 4; i++)
+				d[4 * q + i] = t[i];
+		}
+	}
+}
+
+// vips_linear's band vectors from the kernel's arguments to LDS: thread i brings element i, picked by selects with
+// constant indices (a by-value array indexed at run time would be copied to scratch)
+VH_DEV void arith_constants(const ArithArgs &a, double *ca, double *cb)
+{
+	const int t = tid();
+	double va = 0.0, vb = 0.0;
+#pragma unroll
+	for (int i = 0; i < ARITH_MAX_VECTOR; i++) {
+		va = t == i ? a.a[i] : va;
+		vb = t == i ? a.b[i] : vb;
+	}
+	if (t < ARITH_MAX_VECTOR) {
+		ca[t] = va;
+		cb[t] = vb;
+	}
+	barrier();
+}
+
+constexpr bool arith_binary(int op) { return op >= ARITH_ADD; }
+
+// ---------------------------------------------------------------- one element a lane
+
+template <int OP, typename IN, typename OUT>
+__global__ void __launch_bounds__(ARITH_THREADS)
+arith_general_kernel(ArithArgs a)
+{
+	__shared__ double ca[ARITH_MAX_VECTOR], cb[ARITH_MAX_VECTOR];
+	if constexpr (OP == ARITH_LINEAR)
+		arith_constants(a, ca, cb);
+	const int e = (int) blockIdx.x * ARITH_THREADS + (int) threadIdx.x;
+	if (e >= a.elems)
+		return;
+	const int pel = e / a.bands, k = e - pel * a.bands;
+	const int i1 = a.b1 == 1 ? pel : e, i2 = a.b2 == 1 ? pel : e;
+	double ak = 0.0, bk = 0.0;
+	if constexpr (OP == ARITH_LINEAR) {
+		ak = ca[a.single ? 0 : k];
+		bk = cb[a.single ? 0 : k];
+	}
+	for (int y = (int) blockIdx.y; y < a.height; y += (int) gridDim.y) {
+		IN l = (IN) 0, r = (IN) 0;
+		if (pel < a.w1 && y < a.h1)
+			l = ((const IN *) (a.in + (long long) y * a.in_stride))[i1];
+		if constexpr (arith_binary(OP))
+			if (pel < a.w2 && y < a.h2)
+				r = ((const IN *) (a.in2 + (long long) y * a.in2_stride))[i2];
+		((OUT *) (a.out + (long long) y * a.out_stride))[e] = arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk);
+	}
+}
+
+// ---------------------------------------------------------------- 16 bytes of the output a lane
+
+template <int OP, typename IN, typename OUT>
+__global__ void __launch_bounds__(ARITH_THREADS)
+arith_stream_kernel(ArithArgs a)
+{
+	constexpr int NE = ARITH_GROUP / (int) sizeof(OUT);
+	constexpr int ND = NE * (int) sizeof(IN) / 4; // dwords of an operand's group
+	__shared__ double ca[ARITH_MAX_VECTOR], cb[ARITH_MAX_VECTOR];
+	if constexpr (OP == ARITH_LINEAR)
+		arith_constants(a, ca, cb);
+	const bool vector = OP == ARITH_LINEAR && !a.single;
+	double a0 = 0.0, b0 = 0.0;
+	if constexpr (OP == ARITH_LINEAR) {
+		a0 = ca[0];
+		b0 = cb[0];
+	}
+	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
+	for (unsigned int at = (unsigned int) blockIdx.x * ARITH_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * ARITH_THREADS) {
+		const int y = (int) (at / (unsigned int) a.groups);
+		const int g = (int) (at - (unsigned int) y * (unsigned int) a.groups);
+		const int e0 = g * NE;
+		const int n = min(NE, a.elems - e0); // < NE: the row's ragged end
+		const unsigned long long irow = (unsigned long long) a.in + (unsigned long long) y * a.in_stride;
+		const unsigned long long irow2 = (unsigned long long) a.in2 + (unsigned long long) y * a.in2_stride;
+		const unsigned long long orow = (unsigned long long) a.out + (unsigned long long) y * a.out_stride;
+		int k = vector ? e0 % a.bands : 0;
+		if (n == NE) {
+			unsigned int d[ND], d2[ND], w[4] = { 0, 0, 0, 0 };
+			arith_load<ND>(gptr_in_of(irow), (unsigned int) e0 * (unsigned int) sizeof(IN), d);
+			if constexpr (arith_binary(OP))
+				arith_load<ND>(gptr_in_of(irow2), (unsigned int) e0 * (unsigned int) sizeof(IN), d2);
+#pragma unroll
+			for (int i = 0; i < NE; i++) {
+				const IN l = arith_take<IN, ND>(d, i);
+				IN r = (IN) 0;
+				if constexpr (arith_binary(OP))
+					r = arith_take<IN, ND>(d2, i);
+				double ak = a0, bk = b0;
+				if constexpr (OP == ARITH_LINEAR)
+					if (vector) {
+						ak = ca[k];
+						bk = cb[k];
+						k = k + 1 == a.bands ? 0 : k + 1;
+					}
+				arith_put<OUT>(w, i, arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk));
+			}
+			gstore128(gptr_out_of(orow) + (unsigned int) g * ARITH_GROUP, w);
+		}
+		else {
+			for (int i = 0; i < n; i++) {
+				const IN l = ((const IN *) irow)[e0 + i];
+				IN r = (IN) 0;
+				if constexpr (arith_binary(OP))
+					r = ((const IN *) irow2)[e0 + i];
+				double ak = a0, bk = b0;
+				if constexpr (OP == ARITH_LINEAR)
+					if (vector) {
+						ak = ca[k];
+						bk = cb[k];
+						k = k + 1 == a.bands ? 0 : k + 1;
+					}
+				((OUT *) orow)[e0 + i] = arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk);
+			}
+		}
+	}
+}
+
+// ---------------------------------------------------------------- dispatch
+
+static int arith_rows_grid(int blocks_x, int rows)
+{
+	// enough blocks to fill the part, rows dealt round-robin over grid.y
+	int gy = (ARITH_GRID_BLOCKS + blocks_x - 1) / blocks_x;
+	gy = gy < 1 ? 1 : gy;
+	return gy > rows ? rows : gy;
+}
+
+// every row of the operands starts on a multiple of in_unit, of the output on a multiple of out_unit
+static bool arith_aligned(const ArithArgs &a, bool binary, uintptr_t in_unit, uintptr_t out_unit)
+{
+	uintptr_t in = (uintptr_t) a.in | (uintptr_t) a.in_stride;
+	if (binary)
+		in |= (uintptr_t) a.in2 | (uintptr_t) a.in2_stride;
+	return in % in_unit == 0 && ((uintptr_t) a.out | (uintptr_t) a.out_stride) % out_unit == 0;
+}
+
+// every operand as wide, as tall and of as many bands as the output: element e of a row is element e of every side
+static bool arith_same_shape(const ArithArgs &a, bool binary)
+{
+	const int width = a.elems / a.bands;
+	if (a.b1 != a.bands || a.w1 < width || a.h1 < a.height)
+		return false;
+	return !binary || (a.b2 == a.bands && a.w2 >= width && a.h2 >= a.height);
+}
+
+// Rows that follow one another without a gap on every side are one long row (it starts on a multiple of `bands`
+// elements wherever a row did, so the band of an element does not change): whole images then stream whatever their
+// width, and the ragged end is the image's, not every row's.
+static void arith_join_rows(ArithArgs &a, bool binary, int in_es, int out_es)
+{
+	const long long elems = (long long) a.elems * a.height;
+	if (a.height > 1 && a.in_stride == (long long) a.elems * in_es && a.out_stride == (long long) a.elems * out_es &&
+		(!binary || a.in2_stride == a.in_stride) && a.w1 == a.elems / a.bands && (!binary || a.w2 == a.w1) &&
+		elems * (in_es > out_es ? in_es : out_es) < (1LL << 31)) {
+		a.elems = (int) elems;
+		a.w1 = a.w2 = a.elems / a.bands;
+		a.h1 = a.h2 = a.height = 1;
+		// (one row: nothing is a stride away any more, and the rows' own length must not count in the alignment)
+		a.in_stride = a.in2_stride = a.out_stride = 0;
+	}
+}
+
+static bool arith_stream_ok(const ArithArgs &a, bool binary, int out_es)
+{
+	// rows that start on dwords on every side
+	if (!arith_aligned(a, binary, 4, 4))
+		return false;
+	// (the kernel numbers the groups in 32 bits)
+	const int ne = ARITH_GROUP / out_es;
+	const long long groups = ((long long) a.elems + ne - 1) / ne;
+	return groups * a.height < (1LL << 31);
+}
+
+template <int OP, typename IN, typename OUT>
+static int arith_launch(const char *domain, ArithArgs a)
+{
+	constexpr bool binary = arith_binary(OP);
+	if (!arith_aligned(a, binary, sizeof(IN), sizeof(OUT))) {
+		error(domain, "rows must start on whole elements");
+		return -1;
+	}
+	dim3 block(ARITH_THREADS, 1, 1);
+	bool streams = !getenv("VIPS_HIP_NO_ARITH_STREAM") && arith_same_shape(a, binary);
+	if (streams) {
+		ArithArgs joined = a;
+		arith_join_rows(joined, binary, (int) sizeof(IN), (int) sizeof(OUT));
+		streams = arith_stream_ok(joined, binary, (int) sizeof(OUT));
+		if (streams)
+			a = joined;
+	}
+	if (streams) {
+		constexpr int NE = ARITH_GROUP / (int) sizeof(OUT);
+		a.groups = (a.elems + NE - 1) / NE;
+		const long long blocks = ((long long) a.groups * a.height + ARITH_THREADS - 1) / ARITH_THREADS;
+		dim3 grid((unsigned int) (blocks < ARITH_GRID_BLOCKS ? blocks : ARITH_GRID_BLOCKS), 1, 1);
+		Gate gate("arith_stream");
+		hipLaunchKernelGGL((arith_stream_kernel<OP, IN, OUT>), grid, block, 0, stream(), a);
+	}
+	else {
+		const int bx = (a.elems + ARITH_THREADS - 1) / ARITH_THREADS;
+		dim3 grid(bx, arith_rows_grid(bx, a.height), 1);
+		Gate gate("arith_general");
+		hipLaunchKernelGGL((arith_general_kernel<OP, IN, OUT>), grid, block, 0, stream(), a);
+	}
+	VH_CHECK(hipGetLastError());
+	return 0;
+}
+
+int arith_tile(int what)
+{
+	switch (what) {
+	case 0: return ARITH_THREADS;
+	case 1: return ARITH_GROUP;
+	case 2: return ARITH_GRID_BLOCKS;
+	case 3: return STATS_GRID_BLOCKS;
+	default: return 0;
+	}
+}
+
+typedef unsigned char u8;
+typedef signed char s8;
+typedef unsigned short u16;
+typedef short s16;
+typedef unsigned int u32;
+typedef int s32;
+typedef float f32;
+typedef double f64;
+
+int arith_run(const char *domain, int op, int in_format, int out_format, ArithArgs a)
+{
+	if (a.elems < 1 || a.height < 1 || a.bands < 1 || a.elems % a.bands) {
+		error(domain, "bad image size");
+		return -1;
+	}
+	const long long widest = format_sizeof(in_format) > format_sizeof(out_format) ? format_sizeof(in_format) : format_sizeof(out_format);
+	if ((long long) a.elems * widest >= (1LL << 31)) {
+		error(domain, "image rows too long");
+		return -1;
+	}
+	if (op == ARITH_LINEAR && !a.single && a.bands > ARITH_MAX_VECTOR) {
+		error(domain, "vectors of more than %d elements are outside the HIP path", ARITH_MAX_VECTOR);
+		return -1;
+	}
+#define F(name) VIPS_HIP_FORMAT_##name
+#define GO(OP, FI, TI, FO, TO) \
+	if (op == OP && in_format == F(FI) && out_format == F(FO)) \
+		return arith_launch<OP, TI, TO>(domain, a);
+	// linear.c:425-428, and `uchar`
+	GO(ARITH_LINEAR, UCHAR, u8, FLOAT, f32) GO(ARITH_LINEAR, CHAR, s8, FLOAT, f32) GO(ARITH_LINEAR, USHORT, u16, FLOAT, f32)
+	GO(ARITH_LINEAR, SHORT, s16, FLOAT, f32) GO(ARITH_LINEAR, UINT, u32, FLOAT, f32) GO(ARITH_LINEAR, INT, s32, FLOAT, f32)
+	GO(ARITH_LINEAR, FLOAT, f32, FLOAT, f32) GO(ARITH_LINEAR, DOUBLE, f64, DOUBLE, f64)
+	GO(ARITH_LINEAR, UCHAR, u8, UCHAR, u8) GO(ARITH_LINEAR, CHAR, s8, UCHAR, u8) GO(ARITH_LINEAR, USHORT, u16, UCHAR, u8)
+	GO(ARITH_LINEAR, SHORT, s16, UCHAR, u8) GO(ARITH_LINEAR, UINT, u32, UCHAR, u8) GO(ARITH_LINEAR, INT, s32, UCHAR, u8)
+	GO(ARITH_LINEAR, FLOAT, f32, UCHAR, u8) GO(ARITH_LINEAR, DOUBLE, f64, UCHAR, u8)
+	// invert.c:166-169, abs.c:188-191
+#define SAME(OP) \
+	GO(OP, UCHAR, u8, UCHAR, u8) GO(OP, CHAR, s8, CHAR, s8) GO(OP, USHORT, u16, USHORT, u16) GO(OP, SHORT, s16, SHORT, s16) \
+	GO(OP, UINT, u32, UINT, u32) GO(OP, INT, s32, INT, s32) GO(OP, FLOAT, f32, FLOAT, f32) GO(OP, DOUBLE, f64, DOUBLE, f64)
+	SAME(ARITH_INVERT)
+	SAME(ARITH_ABS)
+#undef SAME
+	// add.c:180-183, multiply.c:197-200
+#define SUM(OP) \
+	GO(OP, UCHAR, u8, USHORT, u16) GO(OP, CHAR, s8, SHORT, s16) GO(OP, USHORT, u16, UINT, u32) GO(OP, SHORT, s16, INT, s32) \
+	GO(OP, UINT, u32, UINT, u32) GO(OP, INT, s32, INT, s32) GO(OP, FLOAT, f32, FLOAT, f32) GO(OP, DOUBLE, f64, DOUBLE, f64)
+	SUM(ARITH_ADD)
+	SUM(ARITH_MULTIPLY)
+#undef SUM
+	// subtract.c:176-179
+	GO(ARITH_SUBTRACT, UCHAR, u8, SHORT, s16) GO(ARITH_SUBTRACT, CHAR, s8, SHORT, s16) GO(ARITH_SUBTRACT, USHORT, u16, INT, s32)
+	GO(ARITH_SUBTRACT, SHORT, s16, INT, s32) GO(ARITH_SUBTRACT, UINT, u32, INT, s32) GO(ARITH_SUBTRACT, INT, s32, INT, s32)
+	GO(ARITH_SUBTRACT, FLOAT, f32, FLOAT, f32) GO(ARITH_SUBTRACT, DOUBLE, f64, DOUBLE, f64)
+	// divide.c:199-202
+	GO(ARITH_DIVIDE, UCHAR, u8, FLOAT, f32) GO(ARITH_DIVIDE, CHAR, s8, FLOAT, f32) GO(ARITH_DIVIDE, USHORT, u16, FLOAT, f32)
+	GO(ARITH_DIVIDE, SHORT, s16, FLOAT, f32) GO(ARITH_DIVIDE, UINT, u32, FLOAT, f32) GO(ARITH_DIVIDE, INT, s32, FLOAT, f32)
+	GO(ARITH_DIVIDE, FLOAT, f32, FLOAT, f32) GO(ARITH_DIVIDE, DOUBLE, f64, DOUBLE, f64)
+#undef GO
+#undef F
+	error(domain, "no kernel for operation %d from format %d to format %d", op, in_format, out_format);
+	return -1;
+}
+
+// ---------------------------------------------------------------- stats
+
+struct StatsArgs {
+	const unsigned char *in;
+	StatsPartial *out;
+	long long stride; // bytes
+	int width, height, bands;
+	int groups; // (stream kernel) groups of 16 / sizeof(T) pels of a row, the ragged one included
+};
+
+template <typename T>
+struct StatsSums {
+	typedef long long Sum;
+	typedef unsigned long long Sum2;
+};
+template <>
+struct StatsSums<float> {
+	typedef double Sum;
+	typedef double Sum2;
+};
+
+// stats.c:247-330 for one band: sum += value; sum2 += (double) value * (double) value; the extremes by > and <, which a
+// NaN never passes.  (The reference starts its extremes at the first value it meets, NaN or not: which value that is
+// depends on how its threads cut the image up, so a NaN there is no contract; here a NaN is never an extreme.)
+template <typename T>
+struct StatsAcc {
+	typename StatsSums<T>::Sum sum;
+	typename StatsSums<T>::Sum2 sum2;
+	T mn, mx;
+	unsigned int imn, imx;
+
+	__device__ __forceinline__ void clear()
+	{
+		sum = 0;
+		sum2 = 0;
+		mn = mx = (T) 0;
+		imn = imx = STATS_NONE;
+	}
+	// (a lane meets its pels in raster order: the strict comparisons keep the first of equals)
+	__device__ __forceinline__ void take(T v, unsigned int index)
+	{
+		sum += v;
+		if constexpr (std::is_floating_point<T>::value)
+			sum2 += (double) v * (double) v;
+		else
+			sum2 += (unsigned long long) ((long long) v * (long long) v);
+		if (imx == STATS_NONE ? v == v : v > mx) {
+			mx = v;
+			imx = index;
+		}
+		if (imn == STATS_NONE ? v == v : v < mn) {
+			mn = v;
+			imn = index;
+		}
+	}
+};
+
+template <typename T>
+VH_DEV unsigned int stats_bits(T v)
+{
+	if constexpr (std::is_floating_point<T>::value)
+		return __builtin_bit_cast(unsigned int, v);
+	else
+		return (unsigned int) (int) v;
+}
+
+// the block's lanes meet in LDS, pairs at half the distance each step; thread 0 writes the partial
+template <typename T>
+VH_DEV void stats_block_reduce(const StatsAcc<T> &acc, StatsPartial *dst)
+{
+	typedef typename StatsSums<T>::Sum Sum;
+	typedef typename StatsSums<T>::Sum2 Sum2;
+	__shared__ Sum s_sum[ARITH_THREADS];
+	__shared__ Sum2 s_sum2[ARITH_THREADS];
+	__shared__ T s_mn[ARITH_THREADS], s_mx[ARITH_THREADS];
+	__shared__ unsigned int s_imn[ARITH_THREADS], s_imx[ARITH_THREADS];
+	const int t = tid();
+	barrier(); // (the band before this one has been read)
+	s_sum[t] = acc.sum;
+	s_sum2[t] = acc.sum2;
+	s_mn[t] = acc.mn;
+	s_mx[t] = acc.mx;
+	s_imn[t] = acc.imn;
+	s_imx[t] = acc.imx;
+	barrier();
+	for (int s = ARITH_THREADS / 2; s > 0; s >>= 1) {
+		if (t < s) {
+			const int o = t + s;
+			s_sum[t] += s_sum[o];
+			s_sum2[t] += s_sum2[o];
+			// the smaller value, of equals the one met first in raster order
+			if (s_imn[o] != STATS_NONE && (s_imn[t] == STATS_NONE || s_mn[o] < s_mn[t] || (s_mn[o] == s_mn[t] && s_imn[o] < s_imn[t]))) {
+				s_mn[t] = s_mn[o];
+				s_imn[t] = s_imn[o];
+			}
+			if (s_imx[o] != STATS_NONE && (s_imx[t] == STATS_NONE || s_mx[o] > s_mx[t] || (s_mx[o] == s_mx[t] && s_imx[o] < s_imx[t]))) {
+				s_mx[t] = s_mx[o];
+				s_imx[t] = s_imx[o];
+			}
+		}
+		barrier();
+	}
+	if (t == 0) {
+		StatsPartial p;
+		if constexpr (std::is_floating_point<T>::value) {
+			p.sum = __builtin_bit_cast(unsigned long long, s_sum[0]);
+			p.sum2 = __builtin_bit_cast(unsigned long long, s_sum2[0]);
+		}
+		else {
+			p.sum = (unsigned long long) s_sum[0];
+			p.sum2 = s_sum2[0];
+		}
+		p.mn = stats_bits<T>(s_mn[0]);
+		p.mx = stats_bits<T>(s_mx[0]);
+		p.imn = s_imn[0];
+		p.imx = s_imx[0];
+		*dst = p;
+	}
+}
+
+template <typename T, int B>
+__global__ void __launch_bounds__(ARITH_THREADS)
+stats_stream_kernel(StatsArgs a)
+{
+	constexpr int NP = ARITH_GROUP / (int) sizeof(T); // pels a lane takes at a time: B groups of 16 bytes
+	StatsAcc<T> acc[B];
+#pragma unroll
+	for (int b = 0; b < B; b++)
+		acc[b].clear();
+	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
+	for (unsigned int at = (unsigned int) blockIdx.x * ARITH_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * ARITH_THREADS) {
+		const int y = (int) (at / (unsigned int) a.groups);
+		const int g = (int) (at - (unsigned int) y * (unsigned int) a.groups);
+		const int p0 = g * NP;
+		const int n = min(NP, a.width - p0);
+		const unsigned long long row = (unsigned long long) a.in + (unsigned long long) y * a.stride;
+		const unsigned int index = (unsigned int) y * (unsigned int) a.width + (unsigned int) p0;
+		if (n == NP) {
+			unsigned int d[4 * B];
+			arith_load<4 * B>(gptr_in_of(row), (unsigned int) g * (unsigned int) (ARITH_GROUP * B), d);
+#pragma unroll
+			for (int j = 0; j < NP * B; j++)
+				acc[j % B].take(arith_take<T, 4 * B>(d, j), index + (unsigned int) (j / B));
+		}
+		else {
+			for (int j = 0; j < n; j++) {
+#pragma unroll
+				for (int b = 0; b < B; b++)
+					acc[b].take(((const T *) row)[(p0 + j) * B + b], index + (unsigned int) j);
+			}
+		}
+	}
+#pragma unroll
+	for (int b = 0; b < B; b++)
+		stats_block_reduce<T>(acc[b], a.out + (size_t) blockIdx.x * B + b);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(ARITH_THREADS)
+stats_general_kernel(StatsArgs a)
+{
+	const int band = (int) blockIdx.y;
+	StatsAcc<T> acc;
+	acc.clear();
+	const unsigned int total = (unsigned int) a.width * (unsigned int) a.height;
+	for (unsigned int at = (unsigned int) blockIdx.x * ARITH_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * ARITH_THREADS) {
+		const unsigned int y = at / (unsigned int) a.width, x = at - y * (unsigned int) a.width;
+		acc.take(((const T *) (a.in + (long long) y * a.stride))[(long long) x * a.bands + band], at);
+	}
+	stats_block_reduce<T>(acc, a.out + (size_t) blockIdx.x * a.bands + band);
+}
+
+// rows that follow one another without a gap are one long row of width * height pels: the raster index of a pel is
+// the same, and an image streams whatever its width
+static bool stats_joined(const _VipsHipImage *in)
+{
+	const long long row = (long long) in->width * in->bands * format_sizeof(in->format);
+	return (long long) in->stride == row && row * in->height < (1LL << 31);
+}
+
+static bool stats_stream_ok(const _VipsHipImage *in)
+{
+	if (getenv("VIPS_HIP_NO_ARITH_STREAM") || in->bands > 4)
+		return false;
+	return ((uintptr_t) in->data | (uintptr_t) (stats_joined(in) ? 0 : in->stride)) % 4 == 0;
+}
+
+static int stats_groups(const _VipsHipImage *in)
+{
+	const int np = ARITH_GROUP / format_sizeof(in->format);
+	return ((stats_joined(in) ? in->width * in->height : in->width) + np - 1) / np;
+}
+
+int stats_blocks(const _VipsHipImage *in)
+{
+	long long blocks;
+	if (stats_stream_ok(in))
+		blocks = ((long long) stats_groups(in) * (stats_joined(in) ? 1 : in->height) + ARITH_THREADS - 1) / ARITH_THREADS;
+	else
+		blocks = ((long long) in->width * in->height + ARITH_THREADS - 1) / ARITH_THREADS;
+	const int cap = stats_stream_ok(in) ? STATS_GRID_BLOCKS : STATS_GRID_BLOCKS / (in->bands < STATS_GRID_BLOCKS ? in->bands : STATS_GRID_BLOCKS);
+	blocks = blocks > cap ? cap : blocks;
+	return (int) (blocks < 1 ? 1 : blocks);
+}
+
+template <typename T>
+static int stats_launch(const char *domain, const _VipsHipImage *in, StatsArgs a)
+{
+	const int blocks = stats_blocks(in);
+	dim3 block(ARITH_THREADS, 1, 1);
+	if (stats_stream_ok(in)) {
+		a.groups = stats_groups(in);
+		if (stats_joined(in)) {
+			a.width *= a.height;
+			a.height = 1;
+		}
+		dim3 grid(blocks, 1, 1);
+		Gate gate("stats_stream");
+		switch (in->bands) {
+		case 1: hipLaunchKernelGGL((stats_stream_kernel<T, 1>), grid, block, 0, stream(), a); break;
+		case 2: hipLaunchKernelGGL((stats_stream_kernel<T, 2>), grid, block, 0, stream(), a); break;
+		case 3: hipLaunchKernelGGL((stats_stream_kernel<T, 3>), grid, block, 0, stream(), a); break;
+		default: hipLaunchKernelGGL((stats_stream_kernel<T, 4>), grid, block, 0, stream(), a); break;
+		}
+	}
+	else {
+		dim3 grid(blocks, in->bands, 1);
+		Gate gate("stats_general");
+		hipLaunchKernelGGL((stats_general_kernel<T>), grid, block, 0, stream(), a);
+	}
+	VH_CHECK(hipGetLastError());
+	return 0;
+}
+
+// Everything has been checked (ops_arith.cpp).
+int stats_run(const char *domain, const _VipsHipImage *in, StatsPartial *slab)
+{
+	// (the kernels number pels in 32 bits, STATS_NONE excluded)
+	if (in->width < 1 || in->height < 1 || in->bands < 1 || in->bands > 65535 || (long long) in->width * in->height >= (1LL << 31) ||
+		(long long) in->width * in->bands * format_sizeof(in->format) >= (1LL << 31)) {
+		error(domain, "image too large");
+		return -1;
+	}
+	if (((uintptr_t) in->data | (uintptr_t) in->stride) % (uintptr_t) format_sizeof(in->format)) {
+		error(domain, "rows must start on whole elements");
+		return -1;
+	}
+	StatsArgs a = {};
+	a.in = (const unsigned char *) in->data;
+	a.out = slab;
+	a.stride = (long long) in->stride;
+	a.width = in->width;
+	a.height = in->height;
+	a.bands = in->bands;
+	switch (in->format) {
+	case VIPS_HIP_FORMAT_UCHAR: return stats_launch<u8>(domain, in, a);
+	case VIPS_HIP_FORMAT_CHAR: return stats_launch<s8>(domain, in, a);
+	case VIPS_HIP_FORMAT_USHORT: return stats_launch<u16>(domain, in, a);
+	case VIPS_HIP_FORMAT_SHORT: return stats_launch<s16>(domain, in, a);
+	case VIPS_HIP_FORMAT_FLOAT: return stats_launch<f32>(domain, in, a);
+	default:
+		error(domain, "no kernel for format %d", in->format);
+		return -1;
+	}
+}
+
+} // namespace vh

@@ -317,4 +317,40 @@ int flatten_run(const char *domain, FlattenArgs a, int format);
 // ... vips_addalpha: every pel's `bands` elements of `es` bytes, then `alpha` (the low es bytes)
 int addalpha_run(const char *domain, const unsigned char *in, long long in_stride, unsigned char *out, long long out_stride,
 	int width, int height, int bands, int es, unsigned long long alpha);
+// arith.hip: the pointwise operations of arithmetic/ on checked geometry (ops_arith.cpp checks everything): ONE launch
+// writes `height` rows of `elems` output elements.  Output element e of row y is made from element e of the operand's
+// row, or -- an operand of one element a pel (b1 / b2 == 1) against `bands` -- from element e / bands; an operand is
+// zero right of its w1 / w2 pels and below its h1 / h2 rows (vips__sizealike: embedded black at (0, 0)).
+enum { ARITH_LINEAR = 0, ARITH_INVERT, ARITH_ABS, ARITH_ADD, ARITH_SUBTRACT, ARITH_MULTIPLY, ARITH_DIVIDE, ARITH_LAST };
+constexpr int ARITH_MAX_VECTOR = 32; // elements of vips_linear's a and b once they differ from band to band
+struct ArithArgs {
+	const unsigned char *in;
+	const unsigned char *in2; // the right-hand operand of the binary operations
+	unsigned char *out;
+	long long in_stride, in2_stride, out_stride; // bytes
+	int elems, height;                            // of the output
+	int bands;                                    // elements a pel of the output
+	int w1, h1, b1, w2, h2, b2;
+	int groups; // (stream kernel) 16-byte groups of an output row, the ragged one included
+	int single; // vips_linear: every element of a and of b the same (LOOP1, linear.c:213-223)
+	float a1, b1f; // ... those, as the float the reference makes of them
+	double a[ARITH_MAX_VECTOR], b[ARITH_MAX_VECTOR]; // a_ready, b_ready (linear.c:181-200)
+};
+int arith_run(const char *domain, int op, int in_format, int out_format, ArithArgs a);
+// arith_tile: 0 the threads of a block, 1 the bytes of a group of the stream kernels, 2 / 3 the most blocks a pointwise /
+// a statistics launch has
+int arith_tile(int what);
+// ... vips_stats' scan (stats.c:247-330) of a whole image of uchar, char, ushort, short or float: every block's
+// partial of every band goes to `slab` (blocks * bands entries, block-major), the host merges them in index order.
+// Sums of integer images are 64-bit integers, of float images doubles (as bits); extremes carry the raster index
+// y * width + x of their first pel, STATS_NONE for none (a band of nothing but NaN).
+constexpr unsigned int STATS_NONE = 0xffffffffu;
+struct StatsPartial {
+	unsigned long long sum, sum2;
+	unsigned int mn, mx;   // the value's bits (integers sign-extended to 32)
+	unsigned int imn, imx;
+};
+// stats_blocks: how many blocks stats_run will launch for this image (the slab's size / bands)
+int stats_blocks(const _VipsHipImage *in);
+int stats_run(const char *domain, const _VipsHipImage *in, StatsPartial *slab);
 } // namespace vh

@@ -565,6 +565,114 @@ class Image(object):
                                 ctypes.byref(self._insert_args(expand, background, shim, align))))
         return Image(out.value)
 
+    # vips_linear / vips_invert / vips_abs, vips_add / vips_subtract / vips_multiply / vips_divide, vips_stats and its
+    # single-number siblings, with pyvips' argument names
+    @staticmethod
+    def linear_args(a, b, uchar=False):
+        """The VipsHipLinear of these arguments: ``a`` and ``b`` numbers or vectors of 1 or ``bands`` elements."""
+        args = _ffi.Linear()
+        lib.vips_hip_linear_defaults(ctypes.byref(args))
+        for name, vector in (("a", a), ("b", b)):
+            vector = [float(v) for v in np.atleast_1d(vector)]
+            if not 1 <= len(vector) <= _ffi.Linear.MAX_VECTOR:
+                raise _ffi.VipsHipError("linear: vectors of 1 to %d elements" % _ffi.Linear.MAX_VECTOR)
+            setattr(args, "n_" + name, len(vector))
+            getattr(args, name)[:len(vector)] = vector
+        args.uchar = int(bool(uchar))
+        return args
+
+    def linear(self, a, b, uchar=False):
+        """vips_linear: ``self * a + b``, float (double for a double image), or uchar with ``uchar=True``; a one-band
+        image against n-element vectors makes n bands."""
+        return self._unary(lib.vips_hip_linear, ctypes.byref(self.linear_args(a, b, uchar)))
+
+    def invert(self):
+        """vips_invert: the format's maximum less the value for unsigned formats, the negative otherwise."""
+        return self._unary(lib.vips_hip_invert)
+
+    def abs(self):
+        """vips_abs."""
+        return self._unary(lib.vips_hip_abs)
+
+    def _binary(self, fn, other):
+        out = ctypes.c_void_p()
+        check(fn(self._h, other._h, ctypes.byref(out)))
+        return Image(out.value)
+
+    def add(self, other):
+        """vips_add: formats, bands (one against n) and sizes are matched as the reference matches them."""
+        return self._binary(lib.vips_hip_add, other)
+
+    def subtract(self, other):
+        return self._binary(lib.vips_hip_subtract, other)
+
+    def multiply(self, other):
+        return self._binary(lib.vips_hip_multiply, other)
+
+    def divide(self, other):
+        """vips_divide: 0 where ``other`` is 0."""
+        return self._binary(lib.vips_hip_divide, other)
+
+    def stats(self):
+        """vips_stats: a (bands + 1, 10) array, row 0 over all bands, columns min, max, sum, sum2, avg, sd, xmin, ymin,
+        xmax, ymax."""
+        out = np.empty((self.bands + 1, 10), np.float64)
+        check(lib.vips_hip_stats(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
+    def avg(self):
+        out = ctypes.c_double()
+        check(lib.vips_hip_avg(self._h, ctypes.byref(out)))
+        return out.value
+
+    def deviate(self):
+        out = ctypes.c_double()
+        check(lib.vips_hip_deviate(self._h, ctypes.byref(out)))
+        return out.value
+
+    def _extreme(self, fn, with_options):
+        out, x, y = ctypes.c_double(), ctypes.c_int(), ctypes.c_int()
+        check(fn(self._h, ctypes.byref(out), ctypes.byref(x), ctypes.byref(y)))
+        if with_options:
+            return out.value, {"x": x.value, "y": y.value}
+        return out.value
+
+    def min(self, with_options=False):
+        """vips_min.  ``with_options``: also return ``{"x", "y"}``, the first pel in raster order that holds it."""
+        return self._extreme(lib.vips_hip_min, with_options)
+
+    def max(self, with_options=False):
+        return self._extreme(lib.vips_hip_max, with_options)
+
+    # the operators, as pyvips spells them: an image on the other side is the two-image operation, a number or a list
+    # of numbers vips_linear.  There is no __rtruediv__: pyvips makes `2 / image` of vips_math2 (pow), which is not on
+    # the device, so that spelling raises TypeError rather than leave it
+    @staticmethod
+    def _numbers(other):
+        return np.atleast_1d(np.asarray(other, np.float64))
+
+    def __add__(self, other):
+        return self.add(other) if isinstance(other, Image) else self.linear(1, other)
+
+    __radd__ = __add__
+
+    def __sub__(self, other):
+        return self.subtract(other) if isinstance(other, Image) else self.linear(1, -self._numbers(other))
+
+    def __rsub__(self, other):
+        return self.linear(-1, other)
+
+    def __mul__(self, other):
+        return self.multiply(other) if isinstance(other, Image) else self.linear(other, 0)
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, other):
+        return self.divide(other) if isinstance(other, Image) else self.linear(1.0 / self._numbers(other), 0)
+
+    def __neg__(self):
+        return self.linear(-1, 0)
+
     def conv(self, mask, scale=1.0, offset=0.0, precision="float", layers=5, cluster=1):
         m = self._mask(mask)
         if precision == "approximate":  # conv.c:99-107
