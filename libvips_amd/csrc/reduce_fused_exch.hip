@@ -21,6 +21,8 @@
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <set>
+#include <utility>
 #include <vector>
 
 namespace vh {
@@ -44,8 +46,24 @@ static constexpr size_t xlds_bytes(int oht)
 // no horizontal pass, no tile end; every row fetched with the default cache policy instead of `nt` (XPROF_L2: what the
 // halo rows -- read by both tiles of a row boundary, at about the same time -- can gain from the L2, as a bound)
 constexpr int XPROF_LOADS = 1, XPROF_NO_H = 2, XPROF_NO_END = 4, XPROF_L2 = 8;
+// ... and the census build (XPROF_CENSUS): the shipped kernel, and thread 0 of every block stamps the chip-wide 100 MHz
+// clock at kernel entry, after the prologue's barrier, when the batch loop is done and after the block's last burst
+// store has been acknowledged, into a slot of XCENSUS_WORDS 64-bit words behind `parts` (the launcher makes the
+// room in this build only, and writes them out: $VIPS_HIP_FUSED_CENSUS, tools/c2_census.py)
+constexpr int XPROF_CENSUS = 16;
+constexpr int XCENSUS_WORDS = 8; // 4 stamps, XCC id, block index, 2 spare: one 64-byte line a tile
 
-template <int D, int NB, int PROF>
+template <int PROF>
+__device__ __forceinline__ void census_stamp(unsigned long long *slot, int k, int t)
+{
+	if constexpr ((PROF & XPROF_CENSUS) != 0) {
+		if (t == 0)
+			slot[k] = __builtin_amdgcn_s_memrealtime();
+	}
+}
+
+// LOOP: the K of the explicit wait in front of the steady batches' refills (MfmaStep::throttle).
+template <int D, int NB, int PROF, int LOOP>
 __device__ __forceinline__ void reduce_fused_x_body(const FusedArgs &a, const MfmaTables *__restrict__ tables,
 	float *parts, int *arrivals, int plain, int *misplaced)
 {
@@ -65,6 +83,8 @@ __device__ __forceinline__ void reduce_fused_x_body(const FusedArgs &a, const Mf
 	if (tile >= a.tiles)
 		return;
 	const int t = threadIdx.x;
+	unsigned long long *census = reinterpret_cast<unsigned long long *>(parts + (size_t) a.tiles * a.oht * XPART) + XCENSUS_WORDS * tile;
+	census_stamp<PROF>(census, 0, t);
 	const int by = tile / a.tiles_x;
 	const int bx = tile - by * a.tiles_x;
 	const int y0 = by * a.oht;
@@ -91,22 +111,14 @@ __device__ __forceinline__ void reduce_fused_x_body(const FusedArgs &a, const Mf
 			acc[o][h] = (float4v){ 0.0f, 0.0f, 0.0f, 0.0f };
 
 	const int ngroups = oh + D - 1;
-	uint2 px[NB][S];
-#pragma unroll
-	for (int b = 0; b < NB; b++)
-		if (b < ngroups)
-			Step::template load_rows<0, S>(a, px[b], row0 + dir * S * b, dir, ca);
-	__syncthreads();
-
 	const bool left_edge = bx == 0, right_edge = bx == a.tiles_x - 1;
-	for (int g0 = 0; g0 < ngroups; g0 += MFMA_SLOTS) {
-		Step::template batch<0, NB>(a, px, g0, ngroups, acc, planes, lane_a, t, row0, dir, ca, 0, oh);
 
-		// ---- horizontal pass over the rows this batch completed (T row r <-> group g0 + r)
+	// ---- the horizontal pass over the rows the batch at g0 completed (T row r <-> group g0 + r)
+	auto hpass = [&](int g0) __attribute__((always_inline)) {
 		const int jlo = max(g0 - (D - 1), 0);
 		const int jhi = min(g0 + MFMA_SLOTS - 1 - (D - 1), oh - 1); // inclusive
 		if (jhi < jlo)
-			continue;
+			return;
 		__syncthreads();
 		if (left_edge || right_edge) {
 			// vips_embed(COPY): the columns beyond the image are its edge column, in every plane row
@@ -163,7 +175,40 @@ __device__ __forceinline__ void reduce_fused_x_body(const FusedArgs &a, const Mf
 			}
 		}
 		__syncthreads();
+	};
+
+	// The row loop.  STEADY batches -- all eight groups there, all eight refills wanted -- run without a branch around
+	// a load (MfmaStep::batch_steady: 15 or 16 of a full tile's 17); a tile too short for one, and every tile's last
+	// one or two batches, run the guarded form.  The two are loops of their own: where their paths joined inside one
+	// loop the compiler would lose count of the loads in flight again and wait for all of them.
+	uint2 px[NB][S];
+	int g0 = 0;
+	if (ngroups >= MFMA_SLOTS + NB) {
+		// (a prologue of its own, without the guards: loads behind a branch here and the steady loop's first waits
+		// are no longer counted ones)
+#pragma unroll
+		for (int b = 0; b < NB; b++)
+			Step::template load_rows<0, S>(a, px[b], row0 + dir * S * b, dir, ca);
+		__syncthreads();
+		census_stamp<PROF>(census, 1, t);
+		for (; g0 + MFMA_SLOTS + NB <= ngroups; g0 += MFMA_SLOTS) {
+			Step::template batch_steady<0, NB, LOOP>(a, px, g0, acc, planes, lane_a, t, row0, dir, ca, 0);
+			hpass(g0);
+		}
 	}
+	else {
+#pragma unroll
+		for (int b = 0; b < NB; b++)
+			if (b < ngroups)
+				Step::template load_rows<0, S>(a, px[b], row0 + dir * S * b, dir, ca);
+		__syncthreads();
+		census_stamp<PROF>(census, 1, t);
+	}
+	for (; g0 < ngroups; g0 += MFMA_SLOTS) {
+		Step::template batch<0, NB>(a, px, g0, ngroups, acc, planes, lane_a, t, row0, dir, ca, 0, oh);
+		hpass(g0);
+	}
+	census_stamp<PROF>(census, 2, t);
 	if (PROF & (XPROF_LOADS | XPROF_NO_END))
 		return;
 
@@ -270,15 +315,30 @@ __device__ __forceinline__ void reduce_fused_x_body(const FusedArgs &a, const Mf
 				*reinterpret_cast<u32x4 *>(dst + 4 * part16) = *reinterpret_cast<const u32x4 *>(src);
 			}
 		}
+		if constexpr ((PROF & XPROF_CENSUS) != 0) {
+			VH_WAIT_VMCNT(0); // (every wave's stores acknowledged)
+			__syncthreads();
+			census_stamp<PROF>(census, 3, t);
+			if (t == 0) {
+				census[4] = (unsigned long long) VH_XCC_ID();
+				census[5] = blockIdx.x;
+			}
+		}
 	}
 }
+
+// The row loop's steady batches in the shipped kernel and its profiling builds: every quad's refill waits until at most
+// 4 of the wave's loads are still in flight (so at most 8 are, of NB * 8 = 32 buffer registers' worth).  Measured
+// interleaved (profiles/c2_row_loop.txt, NOTES R8.1): guarded batches 0.1843-0.1850 ms; steady without an explicit wait
+// 0.1851, K = 20 / 12 / 8: 0.1858 / 0.1858 / 0.1858, K = 0: 0.2017; K = 4: 0.1797-0.1802.
+constexpr int XLOOP = 4;
 
 template <int D, int NB, int OCC>
 __global__ void __launch_bounds__(FUSED_THREADS, OCC)
 reduce_fused_u8x4_mfma_x(FusedArgs a, const MfmaTables *__restrict__ tables, float *parts, int *arrivals, int plain,
 	int *misplaced)
 {
-	reduce_fused_x_body<D, NB, 0>(a, tables, parts, arrivals, plain, misplaced);
+	reduce_fused_x_body<D, NB, 0, XLOOP>(a, tables, parts, arrivals, plain, misplaced);
 }
 
 template <int D, int NB, int OCC, int PROF>
@@ -286,7 +346,7 @@ __global__ void __launch_bounds__(FUSED_THREADS, OCC)
 reduce_exch_prof(FusedArgs a, const MfmaTables *__restrict__ tables, float *parts, int *arrivals, int plain,
 	int *misplaced)
 {
-	reduce_fused_x_body<D, NB, PROF>(a, tables, parts, arrivals, plain, misplaced);
+	reduce_fused_x_body<D, NB, PROF, XLOOP>(a, tables, parts, arrivals, plain, misplaced);
 }
 
 // The straddling outputs: boundary k (0 .. tiles_x: 0 and tiles_x are the image's edges, where one tile holds the
@@ -358,6 +418,50 @@ static bool xcd_placement_holds()
 	return state[dev] == 1;
 }
 
+// A kernel of this file may use 80 KB of dynamic LDS: asked for once per device and kernel, not at every launch.
+static hipError_t allow_big_lds(const void *kern)
+{
+	static std::mutex mutex;
+	static std::set<std::pair<int, const void *>> done;
+	const std::pair<int, const void *> key(current_device(), kern);
+	std::lock_guard<std::mutex> lock(mutex);
+	if (done.count(key))
+		return hipSuccess;
+	const hipError_t err = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+	if (err == hipSuccess)
+		done.insert(key);
+	return err;
+}
+
+// The census build's slots, when $VIPS_HIP_FUSED_CENSUS names a file: one line a tile appended to it -- tile, bx, by,
+// block index, XCC id, the four stamps in ticks of 10 ns after the launch's earliest.  (Profiling only: it waits for
+// the launch.)
+static void census_write(const FusedArgs &a, int tiles_y, const void *d_slots)
+{
+	const char *path = getenv("VIPS_HIP_FUSED_CENSUS");
+	if (!path || !*path)
+		return;
+	std::vector<unsigned long long> slots((size_t) a.tiles * XCENSUS_WORDS);
+	if (hipMemcpyAsync(slots.data(), d_slots, slots.size() * sizeof(slots[0]), hipMemcpyDeviceToHost, stream()) != hipSuccess ||
+		hipStreamSynchronize(stream()) != hipSuccess) {
+		(void) hipGetLastError();
+		return;
+	}
+	unsigned long long first = ~0ull;
+	for (int tile = 0; tile < a.tiles; tile++)
+		first = slots[(size_t) tile * XCENSUS_WORDS] < first ? slots[(size_t) tile * XCENSUS_WORDS] : first;
+	FILE *f = fopen(path, "a");
+	if (!f)
+		return;
+	fprintf(f, "# launch: %d x %d tiles of %d rows; tile bx by block xcc entry prologue loop_done end_done\n", a.tiles_x, tiles_y, a.oht);
+	for (int tile = 0; tile < a.tiles; tile++) {
+		const unsigned long long *s = &slots[(size_t) tile * XCENSUS_WORDS];
+		fprintf(f, "%d %d %d %llu %llu %llu %llu %llu %llu\n", tile, tile % a.tiles_x, tile / a.tiles_x, s[5], s[4], s[0] - first,
+			s[1] - first, s[2] - first, s[3] - first);
+	}
+	fclose(f);
+}
+
 // 0 launched, 1 not this kernel's case, -1 error
 int launch_fused_mfma_x(const FusedArgs &all, const VipsHipRegion *in, const VipsHipRegion *out,
 	const MfmaTables *d_tables)
@@ -393,7 +497,10 @@ int launch_fused_mfma_x(const FusedArgs &all, const VipsHipRegion *in, const Vip
 	const int want = e ? 1 : 384; // (by default only launches that fill most of the part; $VIPS_HIP_FUSED_EXCH=1: any)
 	if (a.tiles < want || a.tiles > 512)
 		return 1;
-	const size_t bytes = (size_t) a.tiles * a.oht * XPART * sizeof(float);
+	const int prof = (a.debug >> 6) & 31;
+	const size_t parts_bytes = (size_t) a.tiles * a.oht * XPART * sizeof(float);
+	const size_t census_bytes = prof == XPROF_CENSUS ? (size_t) a.tiles * XCENSUS_WORDS * sizeof(unsigned long long) : 0;
+	const size_t bytes = parts_bytes + census_bytes;
 	float *parts = (float *) vips_hip_malloc(bytes);
 	if (!parts)
 		return -1;
@@ -438,15 +545,16 @@ int launch_fused_mfma_x(const FusedArgs &all, const VipsHipRegion *in, const Vip
 	const int rows_per_xcd = (tiles_y + 7) / 8;
 	const int grid = 8 * rows_per_xcd * a.tiles_x; // (the kernel's numbering: XCD k takes rows k rows_per_xcd ...)
 	// $VIPS_HIP_FUSED_DEBUG bits 64 / 128 / 256: the profiling builds (XPROF_LOADS / NO_H / NO_END; their output is
-	// not the image's), 512: XPROF_L2 (output unchanged).  (NB = 2 and 1 were measured too, 3-4 % slower than 4:
-	// profiles/NOTES.md R7.1)
+	// not the image's), 512: XPROF_L2, 1024: XPROF_CENSUS (output unchanged).  (NB = 2 and 1 were measured too, 3-4 %
+	// slower than 4: profiles/NOTES.md R7.1)
 	typedef void (*XKernel)(FusedArgs, const MfmaTables *, float *, int *, int, int *);
 	XKernel kern = reduce_fused_u8x4_mfma_x<6, 4, 2>;
-	switch ((a.debug >> 6) & 15) {
+	switch (prof) {
 	case XPROF_LOADS: kern = reduce_exch_prof<6, 4, 2, XPROF_LOADS>; break;
 	case XPROF_NO_H: kern = reduce_exch_prof<6, 4, 2, XPROF_NO_H>; break;
 	case XPROF_NO_END: kern = reduce_exch_prof<6, 4, 2, XPROF_NO_END>; break;
 	case XPROF_L2: kern = reduce_exch_prof<6, 4, 2, XPROF_L2>; break;
+	case XPROF_CENSUS: kern = reduce_exch_prof<6, 4, 2, XPROF_CENSUS>; break;
 	default: break;
 	}
 	int rc = 0;
@@ -454,7 +562,7 @@ int launch_fused_mfma_x(const FusedArgs &all, const VipsHipRegion *in, const Vip
 		Gate gate("reduce_fused_u8_mfma_x");
 		hipError_t err;
 		{
-			err = hipFuncSetAttribute((const void *) kern, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+			err = allow_big_lds((const void *) kern);
 			if (err == hipSuccess)
 				hipLaunchKernelGGL(kern, dim3(grid), dim3(FUSED_THREADS), lds, stream(), a, d_tables, parts, arrivals, plain,
 					misplaced);
@@ -469,6 +577,8 @@ int launch_fused_mfma_x(const FusedArgs &all, const VipsHipRegion *in, const Vip
 		if (hipGetLastError() != hipSuccess)
 			rc = -1;
 	}
+	if (rc == 0 && census_bytes && !(a.debug & 32))
+		census_write(a, tiles_y, reinterpret_cast<const unsigned char *>(parts) + parts_bytes);
 	vips_hip_free(parts); // (the pool hands the block to this thread's LATER work only: ordered on its stream)
 	if (rc)
 		error("reduce", "kernel launch failed");

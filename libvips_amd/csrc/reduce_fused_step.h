@@ -35,6 +35,19 @@ struct FusedArgs {
 template <int D, bool NT, bool LOADS_ONLY, int PLANE>
 struct MfmaStep {
 	static constexpr int S = 8;
+	// quad()'s refill: guarded by `more` (REFILL_GUARDED), or unconditional -- a steady batch, batch_steady() -- behind
+	// an explicit wait that caps the wave at K + 4 loads in flight.  (VH_WAIT_VMCNT spells its argument into the
+	// instruction, so K is a literal here: 4, what the exchange kernel ships with.  The other values measured on it --
+	// no explicit wait, 0, 8, 12, 20 -- are in profiles/c2_row_loop.txt; an arm a value brings them back.)
+	static constexpr int REFILL_GUARDED = -2;
+
+	template <int K>
+	static __device__ __forceinline__ void throttle()
+	{
+		static_assert(K == REFILL_GUARDED || K == 4, "a literal the macro can spell");
+		if constexpr (K == 4)
+			VH_WAIT_VMCNT(4);
+	}
 
 	// Rows first_row + dir * i, I0 <= i < I0 + N.  The launcher only picks these kernels for
 	// windows < 2 GB, so every address is the uniform base (an SGPR pair) plus one 32-bit lane
@@ -61,7 +74,7 @@ struct MfmaStep {
 
 	// One quad (rows 4*Q .. 4*Q+3 of the group) of both pixels; once its B operands exist the
 	// quad's buffer registers are refilled with the rows of group g + NB.
-	template <int ROT, int Q>
+	template <int ROT, int Q, int K = REFILL_GUARDED>
 	static __device__ __forceinline__ void quad(const FusedArgs &a, uint2 (&px)[S], float4v (&acc)[8][2],
 		const half4v *lane_a /* &table[lane & 3] */, bool more, int next_row, int dir, int ca, int cb)
 	{
@@ -69,7 +82,8 @@ struct MfmaStep {
 #pragma unroll
 			for (int i = 4 * Q; i < 4 * Q + 4; i++)
 				VH_USE2(px[i].x, px[i].y);
-			if (more)
+			throttle<K>();
+			if (K != REFILL_GUARDED || more)
 				load_rows<4 * Q, 4>(a, px, next_row, dir, ca);
 			return;
 		}
@@ -97,8 +111,11 @@ struct MfmaStep {
 			b[1] = make_b<1>(r0, r1, r2, r3);
 			b[2] = make_b<2>(r0, r1, r2, r3);
 			b[3] = make_b<3>(r0, r1, r2, r3);
-			if (p == 1 && more)
-				load_rows<4 * Q, 4>(a, px, next_row, dir, ca);
+			if (p == 1) {
+				throttle<K>();
+				if (K != REFILL_GUARDED || more)
+					load_rows<4 * Q, 4>(a, px, next_row, dir, ca);
+			}
 #pragma unroll
 			for (int c = 0; c < 4; c++) {
 				acc[p * 4 + c][0] = __builtin_amdgcn_mfma_f32_4x4x4f16(a0, b[c], acc[p * 4 + c][0], 0, 0, 0);
@@ -210,11 +227,12 @@ struct MfmaStep {
 		if constexpr (ROT < MFMA_SLOTS) {
 			const int g = g0 + ROT;
 			if (g >= 0 && g < ngroups) {
-				// (the branches around a group and around its refill stay: without them -- every
-				// group refilling, the last one with its own rows again -- the compiler's waits
-				// become exact, eight rows stay in flight per wave, and the kernel is SLOWER: 0.1977
-				// against 0.1932 ms; branch-free over whole batches with padded tiles: 0.234.  Fewer
-				// requests in flight is what this part's memory system wants, §3.1 of DESIGN.md)
+				// (the guarded form: the compiler cannot count loads across the joins of these branches and waits
+				// for ALL of a wave's loads twice a batch -- vmcnt(0) inside group 0 and in front of group 4.
+				// The halo kernel runs nothing else: there, at 16 waves a CU and one group in flight per lane,
+				// the branch-free form with exact waits was slower, 0.1977 against 0.1932 ms, round 3.  The
+				// exchange kernel -- 8 waves a CU, NB = 4 -- runs only its head and rest this way; its steady
+				// batches are batch_steady(), measured on that kernel: profiles/c2_row_loop.txt, NOTES R8.1)
 				const bool more = g + NB < ngroups;
 				const int next_row = row0 + dir * S * (g + NB);
 				quad<ROT, 0>(a, px[ROT % NB], acc, lane_a, more, next_row, dir, ca, cb);
@@ -223,6 +241,28 @@ struct MfmaStep {
 				retire<ROT>(acc, planes, ROT, t, j >= 0 && j < oh);
 			}
 			batch<ROT + 1, NB>(a, px, g0, ngroups, acc, planes, lane_a, t, row0, dir, ca, cb, oh);
+		}
+	}
+
+	// A STEADY batch: all eight groups exist and all eight refills are wanted (g0 + MFMA_SLOTS + NB <= ngroups, the
+	// caller's to know), so no branch stands around a load or around the consumption of loaded rows and the
+	// compiler's waits are counted ones -- vmcnt(30) / vmcnt(28) in front of a group's two quads: a quad is consumed
+	// with the 28 newer loads still in flight, unless K says otherwise.  Only the first batch of a tile has slots
+	// that retire nothing (j < 0); that predicate is around LDS stores alone.  What this measured on the exchange
+	// kernel (0.1843-0.1850 ms guarded): everything up to the tile's end 6.5 us shorter without a wait and with
+	// K = 20, 12 and 4, but the whole kernel only with K = 4 (0.1797-0.1802 ms; no wait 0.1851, K = 20 / 12 / 8
+	// 0.1858, K = 0 0.2017): with more than eight loads a wave in flight the launch's end gives the gain back.
+	template <int ROT, int NB, int K>
+	static __device__ __forceinline__ void batch_steady(const FusedArgs &a, uint2 (&px)[NB][S], int g0,
+		float4v (&acc)[8][2], unsigned char *planes, const half4v *lane_a, int t, int row0, int dir, int ca, int cb)
+	{
+		static_assert(K != REFILL_GUARDED, "a steady batch refills unconditionally");
+		if constexpr (ROT < MFMA_SLOTS) {
+			const int next_row = row0 + dir * S * (g0 + ROT + NB);
+			quad<ROT, 0, K>(a, px[ROT % NB], acc, lane_a, true, next_row, dir, ca, cb);
+			quad<ROT, 1, K>(a, px[ROT % NB], acc, lane_a, true, next_row, dir, ca, cb);
+			retire<ROT>(acc, planes, ROT, t, ROT >= D - 1 || g0 > 0);
+			batch_steady<ROT + 1, NB, K>(a, px, g0, acc, planes, lane_a, t, row0, dir, ca, cb);
 		}
 	}
 };
