@@ -2780,3 +2780,224 @@ static void
 vips_abs_hip_init(VipsAbsHip *abs)
 {
 }
+
+/* relational_const_hip / boolean_const_hip / bandjoin_const_hip / extract_band_hip / bandmean_hip / bandbool_hip:
+ * arithmetic/relational.c:560-585, boolean.c:553-576, conversion/bandjoin.c:395-421, extract.c:419-456,
+ * bandmean.c:173-192, bandbool.c:218-246.  Pel by pel: an image over the HBM budget goes through in row strips of the
+ * same rows, each strip one call of the region form straight into the strip's output.  The output's header is the
+ * original's (a one-band image against n constants makes n bands).  Complex images, and more constants than the kernels
+ * keep, are the original's (hip_wants_original). */
+typedef struct _VipsLogicConstHip {
+	VipsHipOp parent_instance;
+	int operation; /* VipsOperationRelational / VipsOperationBoolean */
+	VipsArrayDouble *c;
+	int band, n;
+} VipsLogicConstHip;
+
+typedef VipsLogicConstHip VipsRelationalConstHip;
+typedef VipsLogicConstHip VipsBooleanConstHip;
+typedef VipsLogicConstHip VipsBandjoinConstHip;
+typedef VipsLogicConstHip VipsExtractBandHip;
+typedef VipsLogicConstHip VipsBandmeanHip;
+typedef VipsLogicConstHip VipsBandboolHip;
+
+static const double *
+logic_hip_constants(VipsHipOp *op, int *n)
+{
+	VipsLogicConstHip *logic = (VipsLogicConstHip *) op;
+
+	*n = 0;
+	return logic->c ? vips_array_double_get(logic->c, n) : NULL;
+}
+
+static int
+vips_relational_const_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	int n;
+	const double *c = logic_hip_constants(op, &n);
+
+	return vips_hip_relational_const(in, out, ((VipsLogicConstHip *) op)->operation, c, n);
+}
+
+static int
+vips_boolean_const_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	int n;
+	const double *c = logic_hip_constants(op, &n);
+
+	return vips_hip_boolean_const(in, out, ((VipsLogicConstHip *) op)->operation, c, n);
+}
+
+static int
+vips_bandjoin_const_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	int n;
+	const double *c = logic_hip_constants(op, &n);
+
+	return vips_hip_bandjoin_const(in, out, c, n);
+}
+
+static int
+vips_extract_band_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsLogicConstHip *logic = (VipsLogicConstHip *) op;
+
+	return vips_hip_extract_band(in, out, logic->band, logic->n);
+}
+
+static int
+vips_bandmean_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_bandmean(in, out);
+}
+
+static int
+vips_bandbool_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_bandbool(in, out, ((VipsLogicConstHip *) op)->operation);
+}
+
+/* (no plan: the region forms take the operation's own arguments) */
+static int
+vips_relational_const_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	int n;
+	const double *c = logic_hip_constants(op, &n);
+
+	return vips_hip_relational_const_gen(((VipsLogicConstHip *) op)->operation, c, n, in, out);
+}
+
+static int
+vips_boolean_const_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	int n;
+	const double *c = logic_hip_constants(op, &n);
+
+	return vips_hip_boolean_const_gen(((VipsLogicConstHip *) op)->operation, c, n, in, out);
+}
+
+static int
+vips_bandjoin_const_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	int n;
+	const double *c = logic_hip_constants(op, &n);
+
+	return vips_hip_bandjoin_const_gen(c, n, in, out);
+}
+
+static int
+vips_extract_band_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_extract_band_gen(((VipsLogicConstHip *) op)->band, in, out);
+}
+
+static int
+vips_bandmean_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_bandmean_gen(in, out);
+}
+
+static int
+vips_bandbool_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_bandbool_gen(((VipsLogicConstHip *) op)->operation, in, out);
+}
+
+#define LOGIC_HIP_STRIPS(type_name) \
+	class->strip_open = vips_invert_hip_strip_open; \
+	class->strip_need = vips_linear_hip_strip_need; \
+	class->strip_run = type_name##_strip_run; \
+	class->strip_close = vips_invert_hip_strip_close;
+
+HIP_SUBCLASS_FULL(VipsRelationalConstHip, vips_relational_const_hip, "relational_const_hip",
+	"relational operations against a constant (MI355X)", LOGIC_HIP_STRIPS(vips_relational_const_hip))
+HIP_SUBCLASS_FULL(VipsBooleanConstHip, vips_boolean_const_hip, "boolean_const_hip",
+	"boolean operations against a constant (MI355X)", LOGIC_HIP_STRIPS(vips_boolean_const_hip))
+HIP_SUBCLASS_FULL(VipsBandjoinConstHip, vips_bandjoin_const_hip, "bandjoin_const_hip",
+	"append a constant band to an image (MI355X)", LOGIC_HIP_STRIPS(vips_bandjoin_const_hip))
+HIP_SUBCLASS_FULL(VipsExtractBandHip, vips_extract_band_hip, "extract_band_hip", "extract band from an image (MI355X)",
+	LOGIC_HIP_STRIPS(vips_extract_band_hip))
+HIP_SUBCLASS_FULL(VipsBandmeanHip, vips_bandmean_hip, "bandmean_hip", "band-wise average (MI355X)",
+	LOGIC_HIP_STRIPS(vips_bandmean_hip))
+HIP_SUBCLASS_FULL(VipsBandboolHip, vips_bandbool_hip, "bandbool_hip", "boolean operation across image bands (MI355X)",
+	LOGIC_HIP_STRIPS(vips_bandbool_hip))
+
+static void
+vips_relational_const_hip_args(VipsRelationalConstHipClass *class)
+{
+	VIPS_ARG_ENUM(class, "relational", 200, "Operation", "Relational to perform",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, operation),
+		VIPS_TYPE_OPERATION_RELATIONAL, VIPS_OPERATION_RELATIONAL_EQUAL);
+	VIPS_ARG_BOXED(class, "c", 201, "c", "Array of constants",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, c), VIPS_TYPE_ARRAY_DOUBLE);
+}
+
+static void
+vips_boolean_const_hip_args(VipsBooleanConstHipClass *class)
+{
+	VIPS_ARG_ENUM(class, "boolean", 200, "Operation", "Boolean to perform",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, operation),
+		VIPS_TYPE_OPERATION_BOOLEAN, VIPS_OPERATION_BOOLEAN_AND);
+	VIPS_ARG_BOXED(class, "c", 201, "c", "Array of constants",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, c), VIPS_TYPE_ARRAY_DOUBLE);
+}
+
+static void
+vips_bandjoin_const_hip_args(VipsBandjoinConstHipClass *class)
+{
+	VIPS_ARG_BOXED(class, "c", 12, "Constants", "Array of constants to add",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, c), VIPS_TYPE_ARRAY_DOUBLE);
+}
+
+static void
+vips_extract_band_hip_args(VipsExtractBandHipClass *class)
+{
+	VIPS_ARG_INT(class, "band", 3, "Band", "Band to extract",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, band), 0, VIPS_MAX_COORD, 0);
+	VIPS_ARG_INT(class, "n", 4, "n", "Number of bands to extract",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, n), 1, VIPS_MAX_COORD, 1);
+}
+
+static void
+vips_bandmean_hip_args(VipsBandmeanHipClass *class)
+{
+}
+
+static void
+vips_bandbool_hip_args(VipsBandboolHipClass *class)
+{
+	VIPS_ARG_ENUM(class, "boolean", 200, "Operation", "Boolean to perform",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsLogicConstHip, operation),
+		VIPS_TYPE_OPERATION_BOOLEAN, VIPS_OPERATION_BOOLEAN_AND);
+}
+
+static void
+vips_relational_const_hip_init(VipsRelationalConstHip *logic)
+{
+}
+
+static void
+vips_boolean_const_hip_init(VipsBooleanConstHip *logic)
+{
+}
+
+static void
+vips_bandjoin_const_hip_init(VipsBandjoinConstHip *logic)
+{
+}
+
+static void
+vips_extract_band_hip_init(VipsExtractBandHip *logic)
+{
+	logic->n = 1;
+}
+
+static void
+vips_bandmean_hip_init(VipsBandmeanHip *logic)
+{
+}
+
+static void
+vips_bandbool_hip_init(VipsBandboolHip *logic)
+{
+}

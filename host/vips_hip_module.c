@@ -1557,7 +1557,9 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands;
  *   - embed / gravity of pels of more than 32 bytes (the canvas kernels' ink), flatten to a background of more than
  *     256 bytes;
- *   - linear with a vector of more than VIPS_HIP_ARITH_MAX_VECTOR elements (what the kernels keep in LDS).
+ *   - linear with a vector of more than VIPS_HIP_ARITH_MAX_VECTOR elements (what the kernels keep in LDS);
+ *   - relational_const / boolean_const of more than VIPS_HIP_LOGIC_MAX_VECTOR bands or constants, bandjoin_const of no
+ *     constants or of VIPS_HIP_BANDJOIN_MAX and more (the band kernel's source table).
  */
 static gboolean
 hip_wants_original(VipsHipOp *op, VipsImage *in)
@@ -1626,6 +1628,20 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 				vips_area_unref(VIPS_AREA(vector[i]));
 			}
 		if (longer)
+			return TRUE;
+	}
+	if (strcmp(nick, "relational_const_hip") == 0 || strcmp(nick, "boolean_const_hip") == 0 ||
+		strcmp(nick, "bandjoin_const_hip") == 0) {
+		VipsArrayDouble *c = NULL;
+		int n = 0;
+
+		g_object_get(op, "c", &c, NULL);
+		if (c) {
+			n = VIPS_AREA(c)->n;
+			vips_area_unref(VIPS_AREA(c));
+		}
+		if (strcmp(nick, "bandjoin_const_hip") == 0 ? (n < 1 || n >= VIPS_HIP_BANDJOIN_MAX)
+													: VIPS_MAX(n, in->Bands) > VIPS_HIP_LOGIC_MAX_VECTOR)
 			return TRUE;
 	}
 	if (strcmp(nick, "thumbnail_image_hip") == 0) {
@@ -1811,6 +1827,12 @@ g_module_check_init(GModule *module)
 	vips_linear_hip_get_type();
 	vips_invert_hip_get_type();
 	vips_abs_hip_get_type();
+	vips_relational_const_hip_get_type();
+	vips_boolean_const_hip_get_type();
+	vips_bandjoin_const_hip_get_type();
+	vips_extract_band_hip_get_type();
+	vips_bandmean_hip_get_type();
+	vips_bandbool_hip_get_type();
 
 	/* types registered by a module must never be unloaded */
 	g_module_make_resident(module);

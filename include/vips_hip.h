@@ -1230,6 +1230,105 @@ VIPS_HIP_API int vips_hip_max(VipsHipImage *in, double *out, int *x, int *y);
  * launch has -- for tests that want sizes round them. */
 VIPS_HIP_API int vips_hip_arith_step(int what);
 
+/* ------------------------------------------------ masks: relational / boolean, ifthenelse, the band operations
+ *
+ * vips_relational / vips_relational_const (arithmetic/relational.c), vips_boolean / vips_boolean_const (boolean.c),
+ * vips_ifthenelse with and without `blend` (conversion/ifthenelse.c), vips_bandjoin / vips_bandjoin_const
+ * (bandjoin.c), vips_extract_band (extract.c), vips_bandmean (bandmean.c) and vips_bandbool (bandbool.c) on any
+ * non-complex format, ONE launch an operation (logic.hip), bit for bit the reference's values, format, bands, size and
+ * interpretation.  Complex images are refused with vips_check_noncomplex's words.  Results carry no orientation.
+ */
+#define VIPS_HIP_LOGIC_MAX_VECTOR 32
+#define VIPS_HIP_BANDJOIN_MAX 16
+
+/* VipsOperationRelational, VipsOperationBoolean: the reference's values */
+typedef enum {
+	VIPS_HIP_RELATIONAL_EQUAL = 0,
+	VIPS_HIP_RELATIONAL_NOTEQ,
+	VIPS_HIP_RELATIONAL_LESS,
+	VIPS_HIP_RELATIONAL_LESSEQ,
+	VIPS_HIP_RELATIONAL_MORE,
+	VIPS_HIP_RELATIONAL_MOREEQ,
+	VIPS_HIP_RELATIONAL_LAST
+} VipsHipRelational;
+typedef enum {
+	VIPS_HIP_BOOLEAN_AND = 0,
+	VIPS_HIP_BOOLEAN_OR,
+	VIPS_HIP_BOOLEAN_EOR,
+	VIPS_HIP_BOOLEAN_LSHIFT,
+	VIPS_HIP_BOOLEAN_RSHIFT,
+	VIPS_HIP_BOOLEAN_LAST
+} VipsHipBoolean;
+
+/* The format tables: @boolean 0 relational.c:214-217 (uchar whatever the input), 1 boolean.c:253-256 and
+ * bandbool.c:213-216 (integer formats keep their format, the others give int); -1 for an unknown format.  Host only. */
+VIPS_HIP_API int vips_hip_logic_format(int boolean, int format);
+/* vips_unary_const_build restated (unaryconst.c:54-120) for @n constants against an image of @bands bands:
+ * *@out_bands (a one-band image against n constants makes n bands), c_int / c_double (*@out_bands elements each; either
+ * may be NULL) and *@is_int (every constant survives the conversion to int; may be NULL).  Errors in the reference's
+ * words after @nickname: "vector must have 1 or N elements".  Host only. */
+VIPS_HIP_API int vips_hip_const_plan(const char *nickname, const double *c, int n, int bands, int format, int *out_bands,
+	int *is_int, int *c_int, double *c_double);
+/* vips_arithmetic_build's three steps for the two-image forms (arithmetic.c:436-505), as vips_hip_binary_plan: the
+ * common format, the table applied to it, bands and interpretation by vips__bandalike ("relational: not one band or N
+ * bands"), the larger of each size.  Host only. */
+VIPS_HIP_API int vips_hip_logic_plan(int boolean, int left_width, int left_height, int left_bands, int left_format,
+	int left_interpretation, int right_width, int right_height, int right_bands, int right_format,
+	int right_interpretation, int *format, int *out_format, int *bands, int *interpretation, int *width, int *height);
+/* vips_ifthenelse_build restated (ifthenelse.c:455-520): bands and sizes matched over all three images, *@format the
+ * common format of then and else (the condition goes to uchar), the header the then image's once matched.  Host only. */
+VIPS_HIP_API int vips_hip_ifthenelse_plan(int cond_width, int cond_height, int cond_bands, int cond_format,
+	int cond_interpretation, int then_width, int then_height, int then_bands, int then_format, int then_interpretation,
+	int else_width, int else_height, int else_bands, int else_format, int else_interpretation, int *format, int *bands,
+	int *interpretation, int *width, int *height);
+/* vips_bandary_build for vips_bandjoin (bandary.c:190-245, bandjoin.c:133-160): the common format of all @n images,
+ * the sum of their bands, the largest size, image 0's interpretation.  Host only. */
+VIPS_HIP_API int vips_hip_bandjoin_plan(int n, const int *widths, const int *heights, const int *bands, const int *formats,
+	int interpretation0, int *format, int *out_bands, int *interpretation, int *width, int *height);
+
+/* The generate functions of the one-image operations on a pair of windows of the same size; @out has the bands and
+ * format the operation gives for @in's (extract_band: @out's bands are `n`).  Bytes of @out's frame outside the window
+ * are not touched.  Where rows start on dwords the streaming kernels run, otherwise (and under
+ * VIPS_HIP_NO_LOGIC_STREAM) the one-element-a-lane kernels. */
+VIPS_HIP_API int vips_hip_relational_const_gen(int relational, const double *c, int n, const VipsHipRegion *in,
+	const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_boolean_const_gen(int boolean, const double *c, int n, const VipsHipRegion *in,
+	const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_bandjoin_const_gen(const double *c, int n, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_extract_band_gen(int band, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_bandmean_gen(const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_bandbool_gen(int boolean, const VipsHipRegion *in, const VipsHipRegion *out);
+
+/* Whole images.  Constants: 1 or `bands` of them (a one-band image against n makes n bands).  relational_const compares
+ * with int constants when every constant is integral and the image an integer format (on a uint image the constant
+ * becomes unsigned), with doubles otherwise; boolean_const truncates its constants to int and works on
+ * (unsigned int) pel, so its right shift is logical. */
+VIPS_HIP_API int vips_hip_relational_const(VipsHipImage *in, VipsHipImage **out, int relational, const double *c, int n);
+VIPS_HIP_API int vips_hip_boolean_const(VipsHipImage *in, VipsHipImage **out, int boolean, const double *c, int n);
+/* Two images: an operand whose format is not the common one goes through vips_hip_cast first; then ONE launch, which
+ * indexes a one-band operand by pel and reads zero outside an operand's own rectangle.  The right shift of signed
+ * formats is arithmetic; float and double operands are truncated to int. */
+VIPS_HIP_API int vips_hip_relational(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out, int relational);
+VIPS_HIP_API int vips_hip_boolean(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out, int boolean);
+/* @cond != 0 ? @in1 : @in2, or with @blend (@cond * @in1 + (255 - @cond) * @in2 + 128) / 255 in the reference's int,
+ * unsigned or double arithmetic.  A condition that is not uchar goes through vips_hip_cast (which clips), then and else
+ * to their common format; then ONE launch.  A one-band condition over operands of any number of bands (a mask over
+ * RGB) runs on the streaming kernel too. */
+VIPS_HIP_API int vips_hip_ifthenelse(VipsHipImage *cond, VipsHipImage *in1, VipsHipImage *in2, VipsHipImage **out, int blend);
+/* 1 .. VIPS_HIP_BANDJOIN_MAX images in ONE launch (one image: a copy). */
+VIPS_HIP_API int vips_hip_bandjoin(VipsHipImage **in, int n, VipsHipImage **out);
+/* 0 .. VIPS_HIP_BANDJOIN_MAX - 1 constants appended in the image's format, converted as vips__vector_to_pels
+ * converts them (through float, then vips_cast: 1.5 -> 1, -300 -> -128 on a char image). */
+VIPS_HIP_API int vips_hip_bandjoin_const(VipsHipImage *in, VipsHipImage **out, const double *c, int n);
+/* "extract_band: bad extract band" where @band + @n passes the image's bands. */
+VIPS_HIP_API int vips_hip_extract_band(VipsHipImage *in, VipsHipImage **out, int band, int n);
+VIPS_HIP_API int vips_hip_bandmean(VipsHipImage *in, VipsHipImage **out);
+/* and, or, eor; "bandbool: operator lshift not supported across image bands". */
+VIPS_HIP_API int vips_hip_bandbool(VipsHipImage *in, VipsHipImage **out, int boolean);
+/* 0: the threads of a block of the kernels of logic.hip; 1: the bytes of a group of the streaming kernels; 2: the most
+ * blocks a streaming launch has -- for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_logic_step(int what);
+
 #ifdef __cplusplus
 }
 #endif

@@ -423,6 +423,30 @@ _SIGNATURES = {
     "vips_hip_min": (c_int, [c_void_p, P(c_double), P(c_int), P(c_int)]),
     "vips_hip_max": (c_int, [c_void_p, P(c_double), P(c_int), P(c_int)]),
     "vips_hip_arith_step": (c_int, [c_int]),
+    # relational / boolean, ifthenelse, bandjoin / extract_band / bandmean / bandbool
+    "vips_hip_logic_format": (c_int, [c_int, c_int]),
+    "vips_hip_const_plan": (c_int, [ctypes.c_char_p, P(c_double), c_int, c_int, c_int, P(c_int), P(c_int), P(c_int), P(c_double)]),
+    "vips_hip_logic_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    P(c_int), P(c_int), P(c_int), P(c_int), P(c_int), P(c_int)]),
+    "vips_hip_ifthenelse_plan": (c_int, [c_int] * 15 + [P(c_int)] * 5),
+    "vips_hip_bandjoin_plan": (c_int, [c_int, P(c_int), P(c_int), P(c_int), P(c_int), c_int] + [P(c_int)] * 5),
+    "vips_hip_relational_const_gen": (c_int, [c_int, P(c_double), c_int, RegionP, RegionP]),
+    "vips_hip_boolean_const_gen": (c_int, [c_int, P(c_double), c_int, RegionP, RegionP]),
+    "vips_hip_bandjoin_const_gen": (c_int, [P(c_double), c_int, RegionP, RegionP]),
+    "vips_hip_extract_band_gen": (c_int, [c_int, RegionP, RegionP]),
+    "vips_hip_bandmean_gen": (c_int, [RegionP, RegionP]),
+    "vips_hip_bandbool_gen": (c_int, [c_int, RegionP, RegionP]),
+    "vips_hip_relational_const": (c_int, [c_void_p, P(c_void_p), c_int, P(c_double), c_int]),
+    "vips_hip_boolean_const": (c_int, [c_void_p, P(c_void_p), c_int, P(c_double), c_int]),
+    "vips_hip_relational": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int]),
+    "vips_hip_boolean": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int]),
+    "vips_hip_ifthenelse": (c_int, [c_void_p, c_void_p, c_void_p, P(c_void_p), c_int]),
+    "vips_hip_bandjoin": (c_int, [P(c_void_p), c_int, P(c_void_p)]),
+    "vips_hip_bandjoin_const": (c_int, [c_void_p, P(c_void_p), P(c_double), c_int]),
+    "vips_hip_extract_band": (c_int, [c_void_p, P(c_void_p), c_int, c_int]),
+    "vips_hip_bandmean": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_bandbool": (c_int, [c_void_p, P(c_void_p), c_int]),
+    "vips_hip_logic_step": (c_int, [c_int]),
 }
 
 MISSING = []

@@ -353,4 +353,68 @@ struct StatsPartial {
 // stats_blocks: how many blocks stats_run will launch for this image (the slab's size / bands)
 int stats_blocks(const _VipsHipImage *in);
 int stats_run(const char *domain, const _VipsHipImage *in, StatsPartial *slab);
+// ops_arith.cpp: the common format of two (arithmetic.c:76-109), for every operation that runs vips__formatalike
+int format_common(int a, int b);
+// ... vips_check_noncomplex's words for a complex format; a pair of windows of the same size, non-complex, not in place
+int arithmetic_noncomplex(const char *domain, int format);
+int arithmetic_window_pair(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out);
+// logic.hip: the comparisons and booleans of arithmetic/relational.c and boolean.c on checked geometry (ops_logic.cpp
+// checks everything), with ArithArgs' conventions: ONE launch writes `height` rows of `elems` output elements; output
+// element e of row y is made from element e of an operand's row, or -- an operand of one element a pel (b1 / b2 == 1)
+// against `bands` -- from element e / bands; an operand is zero right of its w1 / w2 pels and below its h1 / h2 rows.
+// in2 == nullptr: the right-hand side is the constants (unaryconst.c:90-120).
+enum { LOGIC_RELATIONAL = 0, LOGIC_BOOLEAN };
+enum { RELATIONAL_EQUAL = 0, RELATIONAL_NOTEQ, RELATIONAL_LESS, RELATIONAL_LESSEQ, RELATIONAL_MORE, RELATIONAL_MOREEQ, RELATIONAL_LAST };
+enum { BOOLEAN_AND = 0, BOOLEAN_OR, BOOLEAN_EOR, BOOLEAN_LSHIFT, BOOLEAN_RSHIFT, BOOLEAN_LAST };
+constexpr int LOGIC_MAX_VECTOR = 32; // constants once they differ from band to band
+struct LogicArgs {
+	const unsigned char *in;
+	const unsigned char *in2;
+	unsigned char *out;
+	long long in_stride, in2_stride, out_stride; // bytes
+	int elems, height;                            // of the output
+	int bands;                                    // elements a pel of the output
+	int w1, h1, b1, w2, h2, b2;
+	int groups; // (stream kernel) 16-byte groups of an output row, the ragged one included
+	int single; // every constant the same
+	int is_int; // relational_const compares with c_int (relational.c:528-529)
+	int c_int[LOGIC_MAX_VECTOR];
+	double c_double[LOGIC_MAX_VECTOR];
+};
+int logic_run(const char *domain, int family, int op, int format, LogicArgs a);
+// ... vips_ifthenelse (conversion/ifthenelse.c): `cond` uchar, of `bands` or of one element a pel; the then and else
+// operands of one format, each of `bands` or of one element a pel; zero outside an operand's rectangle
+struct SelectArgs {
+	const unsigned char *cond, *in, *in2;
+	unsigned char *out;
+	long long cond_stride, in_stride, in2_stride, out_stride;
+	int elems, height, bands;
+	int wc, hc, bc, w1, h1, b1, w2, h2, b2;
+	int groups; // (stream kernel) a lane's units of a row
+};
+int select_run(const char *domain, int format, int blend, SelectArgs a);
+// ... the band operations: BAND_JOIN gathers every output pel from a table of sources -- source i gives the output's
+// bands begin .. end - 1 from its elements first .. of each pel (bandjoin: first == 0 and all its bands; extract_band:
+// one source); a source without a pointer gives `value`, a constant already in the image's format (bandjoin_const);
+// a source is zero outside its rectangle.  BAND_MEAN, BAND_AND, BAND_OR, BAND_EOR fold all pel_elems elements of
+// every pel of source 0 into one.
+enum { BAND_JOIN = 0, BAND_MEAN, BAND_AND, BAND_OR, BAND_EOR };
+constexpr int BAND_MAX_SOURCES = 16;
+struct BandSource {
+	const unsigned char *in;
+	long long stride;
+	unsigned long long value;
+	int pel_elems, first, begin, end, width, height;
+};
+struct BandArgs {
+	unsigned char *out;
+	long long out_stride;
+	int elems, height, out_bands; // of the output
+	int n;
+	int groups; // (stream kernel)
+	BandSource src[BAND_MAX_SOURCES];
+};
+int band_run(const char *domain, int op, int format, BandArgs a);
+// logic_tile: 0 the threads of a block, 1 the bytes of a group of the stream kernels, 2 the most blocks a stream launch has
+int logic_tile(int what);
 } // namespace vh

@@ -42,7 +42,9 @@ struct DeviceBlock {
 
 const char *const NICKNAMES[ARITH_LAST] = { "linear", "invert", "abs", "add", "subtract", "multiply", "divide" };
 
-int check_noncomplex(const char *domain, int format)
+} // namespace
+
+int vh::arithmetic_noncomplex(const char *domain, int format)
 {
 	if (format_iscomplex(format)) {
 		error(domain, "image must be non-complex");
@@ -56,7 +58,7 @@ int check_noncomplex(const char *domain, int format)
 }
 
 // arithmetic.c:76-109
-int format_common(int a, int b)
+int vh::format_common(int a, int b)
 {
 	enum { UC, C, US, S, UI, I };
 	static const int largest[6][6] = {
@@ -74,7 +76,7 @@ int format_common(int a, int b)
 	return largest[a][b];
 }
 
-int check_window_pair(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out)
+int vh::arithmetic_window_pair(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out)
 {
 	if (!in || !out) {
 		error(domain, "null argument");
@@ -82,7 +84,7 @@ int check_window_pair(const char *domain, const VipsHipRegion *in, const VipsHip
 	}
 	if (check_region(domain, in) || check_region(domain, out))
 		return -1;
-	if (check_noncomplex(domain, in->format) || check_noncomplex(domain, out->format))
+	if (arithmetic_noncomplex(domain, in->format) || arithmetic_noncomplex(domain, out->format))
 		return -1;
 	if (in->width != out->width || in->height != out->height) {
 		error(domain, "input and output regions must have the same size");
@@ -94,6 +96,8 @@ int check_window_pair(const char *domain, const VipsHipRegion *in, const VipsHip
 	}
 	return 0;
 }
+
+namespace {
 
 void unary_args(const VipsHipRegion *in, const VipsHipRegion *out, ArithArgs *a)
 {
@@ -117,7 +121,7 @@ int same_gen(int op, const VipsHipRegion *in, const VipsHipRegion *out)
 	const char *domain = NICKNAMES[op];
 	if (ensure_init())
 		return -1;
-	if (check_window_pair(domain, in, out))
+	if (arithmetic_window_pair(domain, in, out))
 		return -1;
 	if (in->bands != out->bands || in->format != out->format) {
 		error(domain, "input and output must have the same bands and format");
@@ -141,7 +145,7 @@ int same_image(int op, VipsHipImage *in, VipsHipImage **out)
 		error(domain, "null argument");
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format))
+	if (arithmetic_noncomplex(domain, in->format))
 		return -1;
 	// abs.c:88-90: vips_unary_copy, a pointer copy
 	if (op == ARITH_ABS && (in->format == VIPS_HIP_FORMAT_UCHAR || in->format == VIPS_HIP_FORMAT_USHORT || in->format == VIPS_HIP_FORMAT_UINT))
@@ -289,7 +293,7 @@ int stats_matrix(const char *domain, VipsHipImage *in, std::vector<double> *matr
 		error(domain, "null argument");
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format)) // stats.c:116, deviate.c:100
+	if (arithmetic_noncomplex(domain, in->format)) // stats.c:116, deviate.c:100
 		return -1;
 	switch (in->format) {
 	case VIPS_HIP_FORMAT_UCHAR:
@@ -364,7 +368,7 @@ int vips_hip_linear_plan(const VipsHipLinear *args, int bands, int format, int *
 		error(domain, "bad arguments");
 		return -1;
 	}
-	if (check_noncomplex(domain, format))
+	if (arithmetic_noncomplex(domain, format))
 		return -1;
 	if (args->n_a < 1 || args->n_a > VIPS_HIP_ARITH_MAX_VECTOR || args->n_b < 1 || args->n_b > VIPS_HIP_ARITH_MAX_VECTOR) {
 		error(domain, "vectors of 1 to %d elements", VIPS_HIP_ARITH_MAX_VECTOR);
@@ -426,7 +430,7 @@ int vips_hip_binary_plan(int op, int left_width, int left_height, int left_bands
 		error(domain, "bad image size");
 		return -1;
 	}
-	if (check_noncomplex(domain, left_format) || check_noncomplex(domain, right_format))
+	if (arithmetic_noncomplex(domain, left_format) || arithmetic_noncomplex(domain, right_format))
 		return -1;
 	*format = format_common(left_format, right_format);
 	*out_format = vips_hip_arith_format(op, *format);
@@ -486,7 +490,7 @@ int vips_hip_linear_gen(const VipsHipLinear *args, const VipsHipRegion *in, cons
 	const char *domain = "linear";
 	if (ensure_init())
 		return -1;
-	if (check_window_pair(domain, in, out))
+	if (arithmetic_window_pair(domain, in, out))
 		return -1;
 	ArithArgs a;
 	unary_args(in, out, &a);

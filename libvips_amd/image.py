@@ -673,6 +673,160 @@ class Image(object):
     def __neg__(self):
         return self.linear(-1, 0)
 
+    # vips_relational / vips_boolean with their _const forms, vips_ifthenelse and the band operations, with pyvips'
+    # argument names: an image on the other side is the two-image operation, a number or a list of numbers the _const one
+    RELATIONAL = {"equal": 0, "noteq": 1, "less": 2, "lesseq": 3, "more": 4, "moreeq": 5}
+    BOOLEAN = {"and": 0, "or": 1, "eor": 2, "lshift": 3, "rshift": 4}
+
+    def _logic(self, image_fn, const_fn, table, op, other, what):
+        op = _enum(table, op, what)
+        if isinstance(other, Image):
+            out = ctypes.c_void_p()
+            check(image_fn(self._h, other._h, ctypes.byref(out), op))
+            return Image(out.value)
+        c = self._numbers(other)
+        return self._unary(const_fn, op, c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(c))
+
+    def relational(self, other, relational):
+        """vips_relational / vips_relational_const: uchar, 255 where the comparison holds."""
+        return self._logic(lib.vips_hip_relational, lib.vips_hip_relational_const, self.RELATIONAL, relational, other, "relational")
+
+    def more(self, other):
+        return self.relational(other, "more")
+
+    def moreeq(self, other):
+        return self.relational(other, "moreeq")
+
+    def less(self, other):
+        return self.relational(other, "less")
+
+    def lesseq(self, other):
+        return self.relational(other, "lesseq")
+
+    def equal(self, other):
+        return self.relational(other, "equal")
+
+    def noteq(self, other):
+        return self.relational(other, "noteq")
+
+    def boolean(self, other, boolean):
+        """vips_boolean / vips_boolean_const: integer formats keep their format, float and double are truncated to int."""
+        return self._logic(lib.vips_hip_boolean, lib.vips_hip_boolean_const, self.BOOLEAN, boolean, other, "boolean")
+
+    def andimage(self, other):
+        return self.boolean(other, "and")
+
+    def orimage(self, other):
+        return self.boolean(other, "or")
+
+    def eorimage(self, other):
+        return self.boolean(other, "eor")
+
+    def lshift(self, other):
+        return self.boolean(other, "lshift")
+
+    def rshift(self, other):
+        return self.boolean(other, "rshift")
+
+    def _imageize(self, match, value):
+        """A number or a list of numbers as pyvips makes an image of it: one pel of that many bands in ``match``'s format
+        (through vips_cast) and interpretation, spread to ``match``'s size on the device (embed, extend "copy"): only the
+        one pel crosses the bus."""
+        c = self._numbers(value).astype(np.float64)
+        pel = Image.new_from_array(c.reshape(1, 1, len(c)), match.interpretation).cast(match.format)
+        return pel.embed(0, 0, match.width, match.height, extend="copy")
+
+    def ifthenelse(self, then, else_, blend=False):
+        """vips_ifthenelse: ``then`` where self is non-zero, ``else_`` elsewhere; ``blend``: self as a 0 .. 255 weight.
+        ``then`` and ``else_`` may be numbers or lists of numbers: they become images in the format of the other one
+        (of self, where both are numbers), as in pyvips."""
+        match = then if isinstance(then, Image) else else_ if isinstance(else_, Image) else self
+        then = then if isinstance(then, Image) else self._imageize(match, then)
+        else_ = else_ if isinstance(else_, Image) else self._imageize(match, else_)
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_ifthenelse(self._h, then._h, else_._h, ctypes.byref(out), int(bool(blend))))
+        return Image(out.value)
+
+    def bandjoin(self, other):
+        """vips_bandjoin of self and an image or a list of images, or -- numbers -- vips_bandjoin_const."""
+        if not isinstance(other, (list, tuple)):
+            other = [other]
+        if all(not isinstance(o, Image) for o in other):
+            c = self._numbers(other)
+            return self._unary(lib.vips_hip_bandjoin_const, c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(c))
+        images = [self] + [o if isinstance(o, Image) else self._imageize(self, o) for o in other]
+        handles = (ctypes.c_void_p * len(images))(*[im._h for im in images])
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_bandjoin(handles, len(images), ctypes.byref(out)))
+        return Image(out.value)
+
+    def extract_band(self, band, n=1):
+        return self._unary(lib.vips_hip_extract_band, int(band), int(n))
+
+    def bandmean(self):
+        return self._unary(lib.vips_hip_bandmean)
+
+    def bandbool(self, boolean):
+        return self._unary(lib.vips_hip_bandbool, _enum(self.BOOLEAN, boolean, "boolean"))
+
+    def bandand(self):
+        return self.bandbool("and")
+
+    def bandor(self):
+        return self.bandbool("or")
+
+    def bandeor(self):
+        return self.bandbool("eor")
+
+    # (__eq__ and __ne__ stay identity: an Image is compared and hashed as an object; equal() / noteq() are the pixels')
+    def __gt__(self, other):
+        return self.more(other)
+
+    def __ge__(self, other):
+        return self.moreeq(other)
+
+    def __lt__(self, other):
+        return self.less(other)
+
+    def __le__(self, other):
+        return self.lesseq(other)
+
+    def __and__(self, other):
+        return self.andimage(other)
+
+    __rand__ = __and__
+
+    def __or__(self, other):
+        return self.orimage(other)
+
+    __ror__ = __or__
+
+    def __xor__(self, other):
+        return self.eorimage(other)
+
+    __rxor__ = __xor__
+
+    def __lshift__(self, other):
+        return self.lshift(other)
+
+    def __rshift__(self, other):
+        return self.rshift(other)
+
+    def __invert__(self):
+        return self.eorimage(-1)  # as pyvips
+
+    def __getitem__(self, arg):
+        """Bands, as pyvips: ``im[1]``, ``im[0:3]`` (unit steps)."""
+        if isinstance(arg, slice):
+            start, stop, step = arg.indices(self.bands)
+            if step != 1 or stop <= start:
+                raise IndexError("bands: a non-empty slice of step 1")
+            return self.extract_band(start, stop - start)
+        i = int(arg)
+        if not -self.bands <= i < self.bands:
+            raise IndexError("band index out of range")
+        return self.extract_band(i % self.bands)
+
     def conv(self, mask, scale=1.0, offset=0.0, precision="float", layers=5, cluster=1):
         m = self._mask(mask)
         if precision == "approximate":  # conv.c:99-107
