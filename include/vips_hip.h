@@ -1329,6 +1329,72 @@ VIPS_HIP_API int vips_hip_bandbool(VipsHipImage *in, VipsHipImage **out, int boo
  * blocks a streaming launch has -- for tests that want sizes round them. */
 VIPS_HIP_API int vips_hip_logic_step(int what);
 
+/* ------------------------------------------------ trim: project, profile, getpoint, find_trim
+ *
+ * vips_project with combine sum (arithmetic/project.c), vips_profile (profile.c), vips_getpoint (getpoint.c) and
+ * vips_find_trim (find_trim.c) on images in HBM: read-only passes, ONE launch each (trim.hip), identical to the reference
+ * in values, format, bands, size and interpretation.  Complex images are refused with vips_check_noncomplex's words
+ * (getpoint: they stay outside the path).  combine max and min stay out: COMBINE_PIXELS (project.c:221-248) assigns the
+ * first pel a worker thread meets and combines every other one with the zero memset left, so there is no answer to be
+ * identical to.
+ */
+#define VIPS_HIP_TRIM_MAX_BACKGROUND 32
+
+/* vips_project_format_table (project.c:99-102): uchar / ushort / uint -> uint, char / short / int -> int, float /
+ * double -> double; -1 for a complex or unknown format.  Host only. */
+VIPS_HIP_API int vips_hip_project_format(int format);
+/* vips_project_build (project.c:128-178): @columns is width x 1, @rows 1 x height, both with the input's bands, the
+ * table's format and interpretation histogram.  Integer sums wrap mod 2^32 as the reference's accumulators do.  Double
+ * sums are added in an order the image's geometry fixes (the reference's order depends on when its threads stop,
+ * project.c:319-361): the same image gives the same bits on every run.  Images of 1 .. 4 bands whose rows start on dwords
+ * take the streaming kernel, everything else (and everything under VIPS_HIP_NO_TRIM_STREAM) one element a lane. */
+VIPS_HIP_API int vips_hip_project(VipsHipImage *in, VipsHipImage **columns, VipsHipImage **rows);
+/* vips_profile_build (profile.c:113-161): @columns width x 1, for every column and band the y of the first non-zero
+ * element or `height`; @rows 1 x height, the x likewise or `width`; both int, interpretation histogram.  Non-zero is C's
+ * `if (p[j])` (profile.c:195): a NaN counts, -0.0 does not. */
+VIPS_HIP_API int vips_hip_profile(VipsHipImage *in, VipsHipImage **columns, VipsHipImage **rows);
+/* vips_getpoint_build (getpoint.c:91-132): the pel at (x, y) as `bands` doubles in @out (@n: its length, at least
+ * `bands`).  One copy of the pel, no launch.  "extract_area: bad extract area" for a point outside the image, as
+ * vips_crop says it. */
+VIPS_HIP_API int vips_hip_getpoint(VipsHipImage *in, int x, int y, double *out, int n);
+
+/* The optional arguments of vips_find_trim (find_trim.c:194-213).  vips_hip_find_trim_defaults(): threshold 10,
+ * n_background 0 (not given: vips_interpretation_max_alpha of the image's interpretation, find_trim.c:95-97), line_art
+ * off.  A threshold below 0 is not taken, as the reference's property refuses it: the default stays. */
+typedef struct {
+	double threshold;
+	int n_background;
+	double background[VIPS_HIP_TRIM_MAX_BACKGROUND];
+	int line_art;
+} VipsHipFindTrim;
+VIPS_HIP_API void vips_hip_find_trim_defaults(VipsHipFindTrim *args);
+/* vips_interpretation_max_alpha (iofuncs/header.c:194-206): find_trim's default background.  Host only. */
+VIPS_HIP_API double vips_hip_find_trim_background(int interpretation);
+/* find_trim.c:145-168 on the two projections of the thresholded image (@columns: `width` sums, @rows: `height`): profile
+ * from both ends.  Nothing set gives left = width, top = height, width = height = 0.  Host only. */
+VIPS_HIP_API int vips_hip_find_trim_finish(const unsigned int *columns, int width, const unsigned int *rows, int height,
+	int *left, int *top, int *out_width, int *out_height);
+/* What vips_linear(1, -background), vips_abs and vips_more_const(threshold) (find_trim.c:131-133) make of every byte value
+ * of a uchar image of @bands bands: table[band * 256 + value] is 255 or 0, from vips_hip_linear_plan's a_ready / b_ready
+ * and single-element rule and the constant as vips_hip_relational_const compares it.  *@fused: the one-launch route
+ * takes this image (1 .. 4 bands, a background of 1 or `bands` values); 0 leaves the table alone.  linear's error for
+ * a background of another length.  Host only: no kernel runs. */
+VIPS_HIP_API int vips_hip_find_trim_table(const VipsHipFindTrim *args, int bands, int interpretation, int *fused,
+	unsigned char *table);
+/* vips_find_trim_build (find_trim.c:72-171).  Two routes that always agree.  Composed: the reference's chain of this
+ * library's own operations -- flatten (an image with alpha), median 3 (unless line_art), linear, abs, more_const, bandor,
+ * project -- then ONE copy of the width + height sums and vips_hip_find_trim_finish on the host; what a member refuses,
+ * find_trim refuses in that member's words.  Fused: uchar images of 1 .. 4 bands after the flatten with a background of
+ * 1 or `bands` values take ONE launch (median, predicate table, bounds) and write nothing the size of the image.
+ * VIPS_HIP_NO_TRIM_FUSED forces the composed route.  @args NULL: the defaults. */
+VIPS_HIP_API int vips_hip_find_trim(VipsHipImage *in, const VipsHipFindTrim *args, int *left, int *top, int *width,
+	int *height);
+/* 0: the threads of a block of the kernels of trim.hip; 1: the bytes of a group of the streaming project kernel; 2: the
+ * rows of a fused tile; 3: the most blocks a project / profile launch has once it needs more than one row of blocks;
+ * 4: the elements of a fused tile's row; 5: the rows a fused block takes; 6: the rows between two meetings of a project
+ * block's waves -- for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_trim_step(int what);
+
 #ifdef __cplusplus
 }
 #endif

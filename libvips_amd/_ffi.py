@@ -135,6 +135,18 @@ class Linear(ctypes.Structure):
     ]
 
 
+class FindTrim(ctypes.Structure):
+    """VipsHipFindTrim (include/vips_hip.h): the optional arguments of vips_find_trim."""
+
+    MAX_BACKGROUND = 32
+    _fields_ = [
+        ("threshold", ctypes.c_double),
+        ("n_background", ctypes.c_int),
+        ("background", ctypes.c_double * 32),
+        ("line_art", ctypes.c_int),
+    ]
+
+
 def _load():
     # PyTorch-ROCm carries its own HIP runtime (soname libamdhip64.so).  Import it first so
     # libvipship.so, which needs that soname, binds to the SAME runtime: device pointers,
@@ -447,6 +459,17 @@ _SIGNATURES = {
     "vips_hip_bandmean": (c_int, [c_void_p, P(c_void_p)]),
     "vips_hip_bandbool": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_logic_step": (c_int, [c_int]),
+    # project / profile / getpoint / find_trim
+    "vips_hip_project_format": (c_int, [c_int]),
+    "vips_hip_project": (c_int, [c_void_p, P(c_void_p), P(c_void_p)]),
+    "vips_hip_profile": (c_int, [c_void_p, P(c_void_p), P(c_void_p)]),
+    "vips_hip_getpoint": (c_int, [c_void_p, c_int, c_int, P(c_double), c_int]),
+    "vips_hip_find_trim_defaults": (None, [P(FindTrim)]),
+    "vips_hip_find_trim_background": (c_double, [c_int]),
+    "vips_hip_find_trim_finish": (c_int, [P(ctypes.c_uint), c_int, P(ctypes.c_uint), c_int] + [P(c_int)] * 4),
+    "vips_hip_find_trim_table": (c_int, [P(FindTrim), c_int, c_int, P(c_int), P(ctypes.c_ubyte)]),
+    "vips_hip_find_trim": (c_int, [c_void_p, P(FindTrim)] + [P(c_int)] * 4),
+    "vips_hip_trim_step": (c_int, [c_int]),
 }
 
 MISSING = []

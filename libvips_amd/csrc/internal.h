@@ -417,4 +417,24 @@ struct BandArgs {
 int band_run(const char *domain, int op, int format, BandArgs a);
 // logic_tile: 0 the threads of a block, 1 the bytes of a group of the stream kernels, 2 the most blocks a stream launch has
 int logic_tile(int what);
+// trim.hip: vips_project's sums (project.c:221-298, combine sum) of a whole image in ONE launch.  Integer formats: the
+// sums are ADDED to `columns` (width * bands) and `rows` (height * bands) 32-bit words, zero before the launch.  float
+// and double: the blocks' partials go to col_part (grid[1] rows of width * bands doubles) and row_part (grid[0] rows of
+// height * bands), project_grid() giving the grid; the block that takes the last ticket (*ticket zero before the launch)
+// adds them in index order and writes both outputs.
+void project_grid(const _VipsHipImage *in, int grid[3]);
+int project_run(const char *domain, const _VipsHipImage *in, void *columns, void *rows, double *col_part, double *row_part,
+	unsigned int *ticket);
+// ... vips_profile's scan (profile.c:184-254): integer minima into `columns` (width * bands ints holding `height` before
+// the launch) and `rows` (height * bands ints holding `width`)
+int profile_run(const char *domain, const _VipsHipImage *in, int *columns, int *rows);
+// ... vips_find_trim's scan of a uchar image of 1 .. 4 bands in ONE launch: the 3 x 3 median (`median`; else the pel
+// itself), table[band * 256 + value] != 0 as the predicate of an element, and into bounds[0 .. 3] the maxima of
+// width - x, x + 1, height - y, y + 1 over the pels with an element whose predicate holds (zero before the launch:
+// zero after it says no pel is set).  `table` (256 * bands bytes) and `bounds` are device memory.
+int trim_fused_run(const char *domain, const _VipsHipImage *in, int median, const unsigned char *table, unsigned int *bounds);
+// trim_tile: 0 the threads of a block, 1 the bytes of a group of project_stream, 2 the rows of a fused tile, 3 the most
+// blocks a project / profile launch has once more than one row of blocks is needed, 4 the elements of a fused tile's row,
+// 5 the rows a fused block takes, 6 the rows between two meetings of a project / profile block's waves
+int trim_tile(int what);
 } // namespace vh

@@ -644,6 +644,52 @@ class Image(object):
     def max(self, with_options=False):
         return self._extreme(lib.vips_hip_max, with_options)
 
+    # libvips/arithmetic: vips_project / vips_profile / vips_getpoint / vips_find_trim
+    def _pair(self, fn):
+        columns, rows = ctypes.c_void_p(), ctypes.c_void_p()
+        check(fn(self._h, ctypes.byref(columns), ctypes.byref(rows)))
+        return Image(columns.value), Image(rows.value)
+
+    def project(self):
+        """vips_project: ``(columns, rows)``, the sums of every column (width x 1) and of every row (1 x height), band by
+        band; uint, int or double, interpretation histogram."""
+        return self._pair(lib.vips_hip_project)
+
+    def profile(self):
+        """vips_profile: ``(columns, rows)``, for every column the y of its first non-zero element (or the height), for
+        every row the x (or the width); int, interpretation histogram."""
+        return self._pair(lib.vips_hip_profile)
+
+    def getpoint(self, x, y):
+        """vips_getpoint: the pel at (x, y) as a list of ``bands`` floats."""
+        out = (ctypes.c_double * self.bands)()
+        check(lib.vips_hip_getpoint(self._h, int(x), int(y), out, self.bands))
+        return list(out)
+
+    @staticmethod
+    def find_trim_args(threshold=10.0, background=None, line_art=False):
+        """The VipsHipFindTrim of these arguments."""
+        args = _ffi.FindTrim()
+        lib.vips_hip_find_trim_defaults(ctypes.byref(args))
+        args.threshold = float(threshold)
+        args.line_art = int(bool(line_art))
+        if background is not None:
+            background = [float(v) for v in np.atleast_1d(background)]
+            if len(background) > _ffi.FindTrim.MAX_BACKGROUND:
+                raise _ffi.VipsHipError("find_trim: background of more than %d elements" % _ffi.FindTrim.MAX_BACKGROUND)
+            args.n_background = len(background)
+            args.background[:len(background)] = background
+        return args
+
+    def find_trim(self, threshold=10.0, background=None, line_art=False):
+        """vips_find_trim: ``(left, top, width, height)`` of what differs from ``background`` (default: the
+        interpretation's white) by more than ``threshold`` after a 3 x 3 median (``line_art``: without it);
+        ``(width, height, 0, 0)`` of the image when nothing does.  ``page = scan.extract_area(*scan.find_trim())``."""
+        box = [ctypes.c_int() for _ in range(4)]
+        check(lib.vips_hip_find_trim(self._h, ctypes.byref(self.find_trim_args(threshold, background, line_art)),
+                                     *[ctypes.byref(v) for v in box]))
+        return tuple(v.value for v in box)
+
     # the operators, as pyvips spells them: an image on the other side is the two-image operation, a number or a list
     # of numbers vips_linear.  There is no __rtruediv__: pyvips makes `2 / image` of vips_math2 (pow), which is not on
     # the device, so that spelling raises TypeError rather than leave it
