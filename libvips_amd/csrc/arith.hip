@@ -1,19 +1,11 @@
 // vips_linear, vips_invert, vips_abs (arithmetic/linear.c, invert.c, abs.c), vips_add, vips_subtract, vips_multiply,
 // vips_divide (add.c, subtract.c, multiply.c, divide.c) and the scan of vips_stats (stats.c) on the device (gfx950).
 //
-// The pointwise operations are ONE launch that writes every output byte once:
-//
-//   arith_stream<OP, IN, OUT>   lanes on consecutive 16-byte groups of an OUTPUT row: 16 / sizeof(OUT) elements, whose
-//                               operands are 16 * sizeof(IN) / sizeof(OUT) bytes of the input row -- 4 to 128, always
-//                               whole dwords at a dword offset, so with rows that start on dwords on every side the lane
-//                               loads them as aligned dwords (global_load_dwordx4 where there are four) and stores one
-//                               global_store_dwordx4.  The rows' groups are dealt to the lanes as one sequence; a row's
-//                               ragged last group goes element by element inside the same launch.  The constants of
-//                               vips_linear's band vectors lie in LDS and are picked by (element index) mod bands.
-//   arith_general<OP, IN, OUT>  one element a lane: defines correctness and takes what the stream declines -- rows that
-//                               do not start on dwords, a one-band operand against n bands (indexed by pel), operands
-//                               of different sizes (zero outside an operand's rectangle: vips__sizealike's black embed
-//                               at (0, 0), arithmetic.c:139-171) -- and everything under VIPS_HIP_NO_ARITH_STREAM.
+// The pointwise operations are ONE launch that writes every output byte once: pointwise.h's stream kernel
+// (arith_stream) where the rows start on dwords on every side and every operand has the output's shape, its one-element-
+// a-lane kernel (arith_general) for the rest and for everything under VIPS_HIP_NO_ARITH_STREAM.  This file gives them
+// the expressions (arith_elem), the policy (ArithOp: vips_linear's band vectors are the constants staged to LDS) and
+// the table of formats (arith_run).
 //
 // The arithmetic is the reference's, expression by expression (arith_elem below cites each); the file is compiled with
 // -ffp-contract=off, so multiplies and adds stay separate as in the reference's baseline x86-64 code, and float
@@ -31,20 +23,11 @@
 //                        a slab, the host merges the slab in index order: no floating atomics, the order depends on
 //                        the image's geometry alone.
 //   stats_general<T>     any band count and any row start: block (x, band), one element a lane and step.
-#include "gcn.h"
-#include "internal.h"
-#include "kernel_stmt.h"
-
-#include <cstdint>
-#include <cstdlib>
-#include <type_traits>
+#include "pointwise.h"
 
 namespace vh {
 
-constexpr int ARITH_THREADS = 256;
-constexpr int ARITH_GROUP = 16;            // bytes of the output a lane makes at a time
-constexpr int ARITH_GRID_BLOCKS = 256 * 8; // of a stream launch (as canvas_stream)
-constexpr int STATS_GRID_BLOCKS = 1024;    // four a CU, as hist_rects
+constexpr int STATS_GRID_BLOCKS = 1024; // four a CU, as hist_rects
 
 // ---------------------------------------------------------------- the reference's expressions
 
@@ -134,55 +117,7 @@ VH_DEV OUT arith_elem(IN x, IN y, bool single, float a1, float b1, double ak, do
 	}
 }
 
-// ---------------------------------------------------------------- registers <-> elements
-
-// element i (a constant once the loops are unrolled) of the dwords of a group
-template <typename T, int ND>
-VH_DEV T arith_take(const unsigned int (&d)[ND], int i)
-{
-	if constexpr (sizeof(T) == 1)
-		return (T) (d[i >> 2] >> (8 * (i & 3)));
-	else if constexpr (sizeof(T) == 2)
-		return (T) (d[i >> 1] >> (16 * (i & 1)));
-	else if constexpr (sizeof(T) == 4)
-		return __builtin_bit_cast(T, d[i]);
-	else
-		return __builtin_bit_cast(T, (unsigned long long) d[2 * i] | ((unsigned long long) d[2 * i + 1] << 32));
-}
-
-template <typename T>
-VH_DEV void arith_put(unsigned int (&w)[4], int i, T v)
-{
-	if constexpr (sizeof(T) == 1)
-		w[i >> 2] |= (unsigned int) (unsigned char) v << (8 * (i & 3));
-	else if constexpr (sizeof(T) == 2)
-		w[i >> 1] |= (unsigned int) (unsigned short) v << (16 * (i & 1));
-	else if constexpr (sizeof(T) == 4)
-		w[i] = __builtin_bit_cast(unsigned int, v);
-	else {
-		const unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
-		w[2 * i] = (unsigned int) bits;
-		w[2 * i + 1] = (unsigned int) (bits >> 32);
-	}
-}
-
-// ND dwords (1, 2 or a multiple of 4) at a dword-aligned offset
-template <int ND>
-VH_DEV void arith_load(gptr_in base, unsigned int off, unsigned int (&d)[ND])
-{
-	if constexpr (ND < 4)
-		gload_dwords<ND>(base, off, d);
-	else {
-#pragma unroll
-		for (int q = 0; q < ND / 4; q++) {
-			unsigned int t[4];
-			gload128(base, off + 16u * (unsigned int) q, t);
-#pragma unroll
-			for (int i = 0; i < 4; i++)
-				d[4 * q + i] = t[i];
-		}
-	}
-}
+// ---------------------------------------------------------------- the policy
 
 // vips_linear's band vectors from the kernel's arguments to LDS: thread i brings element i, picked by selects with
 // constant indices (a by-value array indexed at run time would be copied to scratch)
@@ -204,214 +139,29 @@ VH_DEV void arith_constants(const ArithArgs &a, double *ca, double *cb)
 
 constexpr bool arith_binary(int op) { return op >= ARITH_ADD; }
 
-// ---------------------------------------------------------------- one element a lane
-
-template <int OP, typename IN, typename OUT>
-__global__ void __launch_bounds__(ARITH_THREADS)
-arith_general_kernel(ArithArgs a)
-{
-	__shared__ double ca[ARITH_MAX_VECTOR], cb[ARITH_MAX_VECTOR];
-	if constexpr (OP == ARITH_LINEAR)
-		arith_constants(a, ca, cb);
-	const int e = (int) blockIdx.x * ARITH_THREADS + (int) threadIdx.x;
-	if (e >= a.elems)
-		return;
-	const int pel = e / a.bands, k = e - pel * a.bands;
-	const int i1 = a.b1 == 1 ? pel : e, i2 = a.b2 == 1 ? pel : e;
-	double ak = 0.0, bk = 0.0;
-	if constexpr (OP == ARITH_LINEAR) {
-		ak = ca[a.single ? 0 : k];
-		bk = cb[a.single ? 0 : k];
-	}
-	for (int y = (int) blockIdx.y; y < a.height; y += (int) gridDim.y) {
-		IN l = (IN) 0, r = (IN) 0;
-		if (pel < a.w1 && y < a.h1)
-			l = ((const IN *) (a.in + (long long) y * a.in_stride))[i1];
-		if constexpr (arith_binary(OP))
-			if (pel < a.w2 && y < a.h2)
-				r = ((const IN *) (a.in2 + (long long) y * a.in2_stride))[i2];
-		((OUT *) (a.out + (long long) y * a.out_stride))[e] = arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk);
-	}
-}
-
-// ---------------------------------------------------------------- 16 bytes of the output a lane
-
-template <int OP, typename IN, typename OUT>
-__global__ void __launch_bounds__(ARITH_THREADS)
-arith_stream_kernel(ArithArgs a)
-{
-	constexpr int NE = ARITH_GROUP / (int) sizeof(OUT);
-	constexpr int ND = NE * (int) sizeof(IN) / 4; // dwords of an operand's group
-	__shared__ double ca[ARITH_MAX_VECTOR], cb[ARITH_MAX_VECTOR];
-	if constexpr (OP == ARITH_LINEAR)
-		arith_constants(a, ca, cb);
-	const bool vector = OP == ARITH_LINEAR && !a.single;
-	double a0 = 0.0, b0 = 0.0;
-	if constexpr (OP == ARITH_LINEAR) {
-		a0 = ca[0];
-		b0 = cb[0];
-	}
-	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
-	for (unsigned int at = (unsigned int) blockIdx.x * ARITH_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * ARITH_THREADS) {
-		const int y = (int) (at / (unsigned int) a.groups);
-		const int g = (int) (at - (unsigned int) y * (unsigned int) a.groups);
-		const int e0 = g * NE;
-		const int n = min(NE, a.elems - e0); // < NE: the row's ragged end
-		const unsigned long long irow = (unsigned long long) a.in + (unsigned long long) y * a.in_stride;
-		const unsigned long long irow2 = (unsigned long long) a.in2 + (unsigned long long) y * a.in2_stride;
-		const unsigned long long orow = (unsigned long long) a.out + (unsigned long long) y * a.out_stride;
-		int k = vector ? e0 % a.bands : 0;
-		if (n == NE) {
-			unsigned int d[ND], d2[ND], w[4] = { 0, 0, 0, 0 };
-			arith_load<ND>(gptr_in_of(irow), (unsigned int) e0 * (unsigned int) sizeof(IN), d);
-			if constexpr (arith_binary(OP))
-				arith_load<ND>(gptr_in_of(irow2), (unsigned int) e0 * (unsigned int) sizeof(IN), d2);
-#pragma unroll
-			for (int i = 0; i < NE; i++) {
-				const IN l = arith_take<IN, ND>(d, i);
-				IN r = (IN) 0;
-				if constexpr (arith_binary(OP))
-					r = arith_take<IN, ND>(d2, i);
-				double ak = a0, bk = b0;
-				if constexpr (OP == ARITH_LINEAR)
-					if (vector) {
-						ak = ca[k];
-						bk = cb[k];
-						k = k + 1 == a.bands ? 0 : k + 1;
-					}
-				arith_put<OUT>(w, i, arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk));
-			}
-			gstore128(gptr_out_of(orow) + (unsigned int) g * ARITH_GROUP, w);
-		}
-		else {
-			for (int i = 0; i < n; i++) {
-				const IN l = ((const IN *) irow)[e0 + i];
-				IN r = (IN) 0;
-				if constexpr (arith_binary(OP))
-					r = ((const IN *) irow2)[e0 + i];
-				double ak = a0, bk = b0;
-				if constexpr (OP == ARITH_LINEAR)
-					if (vector) {
-						ak = ca[k];
-						bk = cb[k];
-						k = k + 1 == a.bands ? 0 : k + 1;
-					}
-				((OUT *) orow)[e0 + i] = arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk);
-			}
-		}
-	}
-}
-
-// ---------------------------------------------------------------- dispatch
-
-static int arith_rows_grid(int blocks_x, int rows)
-{
-	// enough blocks to fill the part, rows dealt round-robin over grid.y
-	int gy = (ARITH_GRID_BLOCKS + blocks_x - 1) / blocks_x;
-	gy = gy < 1 ? 1 : gy;
-	return gy > rows ? rows : gy;
-}
-
-// every row of the operands starts on a multiple of in_unit, of the output on a multiple of out_unit
-static bool arith_aligned(const ArithArgs &a, bool binary, uintptr_t in_unit, uintptr_t out_unit)
-{
-	uintptr_t in = (uintptr_t) a.in | (uintptr_t) a.in_stride;
-	if (binary)
-		in |= (uintptr_t) a.in2 | (uintptr_t) a.in2_stride;
-	return in % in_unit == 0 && ((uintptr_t) a.out | (uintptr_t) a.out_stride) % out_unit == 0;
-}
-
-// every operand as wide, as tall and of as many bands as the output: element e of a row is element e of every side
-static bool arith_same_shape(const ArithArgs &a, bool binary)
-{
-	const int width = a.elems / a.bands;
-	if (a.b1 != a.bands || a.w1 < width || a.h1 < a.height)
-		return false;
-	return !binary || (a.b2 == a.bands && a.w2 >= width && a.h2 >= a.height);
-}
-
-// Rows that follow one another without a gap on every side are one long row (it starts on a multiple of `bands`
-// elements wherever a row did, so the band of an element does not change): whole images then stream whatever their
-// width, and the ragged end is the image's, not every row's.
-static void arith_join_rows(ArithArgs &a, bool binary, int in_es, int out_es)
-{
-	const long long elems = (long long) a.elems * a.height;
-	if (a.height > 1 && a.in_stride == (long long) a.elems * in_es && a.out_stride == (long long) a.elems * out_es &&
-		(!binary || a.in2_stride == a.in_stride) && a.w1 == a.elems / a.bands && (!binary || a.w2 == a.w1) &&
-		elems * (in_es > out_es ? in_es : out_es) < (1LL << 31)) {
-		a.elems = (int) elems;
-		a.w1 = a.w2 = a.elems / a.bands;
-		a.h1 = a.h2 = a.height = 1;
-		// (one row: nothing is a stride away any more, and the rows' own length must not count in the alignment)
-		a.in_stride = a.in2_stride = a.out_stride = 0;
-	}
-}
-
-static bool arith_stream_ok(const ArithArgs &a, bool binary, int out_es)
-{
-	// rows that start on dwords on every side
-	if (!arith_aligned(a, binary, 4, 4))
-		return false;
-	// (the kernel numbers the groups in 32 bits)
-	const int ne = ARITH_GROUP / out_es;
-	const long long groups = ((long long) a.elems + ne - 1) / ne;
-	return groups * a.height < (1LL << 31);
-}
-
-template <int OP, typename IN, typename OUT>
-static int arith_launch(const char *domain, ArithArgs a)
-{
-	constexpr bool binary = arith_binary(OP);
-	if (!arith_aligned(a, binary, sizeof(IN), sizeof(OUT))) {
-		error(domain, "rows must start on whole elements");
-		return -1;
-	}
-	dim3 block(ARITH_THREADS, 1, 1);
-	bool streams = !getenv("VIPS_HIP_NO_ARITH_STREAM") && arith_same_shape(a, binary);
-	if (streams) {
-		ArithArgs joined = a;
-		arith_join_rows(joined, binary, (int) sizeof(IN), (int) sizeof(OUT));
-		streams = arith_stream_ok(joined, binary, (int) sizeof(OUT));
-		if (streams)
-			a = joined;
-	}
-	if (streams) {
-		constexpr int NE = ARITH_GROUP / (int) sizeof(OUT);
-		a.groups = (a.elems + NE - 1) / NE;
-		const long long blocks = ((long long) a.groups * a.height + ARITH_THREADS - 1) / ARITH_THREADS;
-		dim3 grid((unsigned int) (blocks < ARITH_GRID_BLOCKS ? blocks : ARITH_GRID_BLOCKS), 1, 1);
-		Gate gate("arith_stream");
-		hipLaunchKernelGGL((arith_stream_kernel<OP, IN, OUT>), grid, block, 0, stream(), a);
-	}
-	else {
-		const int bx = (a.elems + ARITH_THREADS - 1) / ARITH_THREADS;
-		dim3 grid(bx, arith_rows_grid(bx, a.height), 1);
-		Gate gate("arith_general");
-		hipLaunchKernelGGL((arith_general_kernel<OP, IN, OUT>), grid, block, 0, stream(), a);
-	}
-	VH_CHECK(hipGetLastError());
-	return 0;
-}
+template <int OP, typename IN_, typename OUT_>
+struct ArithOp {
+	typedef IN_ IN;
+	typedef OUT_ OUT;
+	typedef ArithArgs Args;
+	typedef double CA, CB;
+	static constexpr int MAX_VECTOR = ARITH_MAX_VECTOR;
+	static constexpr bool binary = arith_binary(OP);
+	static constexpr bool constants = OP == ARITH_LINEAR;
+	VH_DEV void stage(const ArithArgs &a, double *ca, double *cb) { arith_constants(a, ca, cb); }
+	VH_DEV OUT elem(const ArithArgs &a, IN l, IN r, double ak, double bk) { return arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk); }
+};
 
 int arith_tile(int what)
 {
 	switch (what) {
-	case 0: return ARITH_THREADS;
-	case 1: return ARITH_GROUP;
-	case 2: return ARITH_GRID_BLOCKS;
+	case 0: return POINTWISE_THREADS;
+	case 1: return POINTWISE_GROUP;
+	case 2: return POINTWISE_GRID_BLOCKS;
 	case 3: return STATS_GRID_BLOCKS;
 	default: return 0;
 	}
 }
-
-typedef unsigned char u8;
-typedef signed char s8;
-typedef unsigned short u16;
-typedef short s16;
-typedef unsigned int u32;
-typedef int s32;
-typedef float f32;
-typedef double f64;
 
 int arith_run(const char *domain, int op, int in_format, int out_format, ArithArgs a)
 {
@@ -431,7 +181,7 @@ int arith_run(const char *domain, int op, int in_format, int out_format, ArithAr
 #define F(name) VIPS_HIP_FORMAT_##name
 #define GO(OP, FI, TI, FO, TO) \
 	if (op == OP && in_format == F(FI) && out_format == F(FO)) \
-		return arith_launch<OP, TI, TO>(domain, a);
+		return pointwise_launch<ArithOp<OP, TI, TO>>(domain, a, "arith_stream", "arith_general", "VIPS_HIP_NO_ARITH_STREAM");
 	// linear.c:425-428, and `uchar`
 	GO(ARITH_LINEAR, UCHAR, u8, FLOAT, f32) GO(ARITH_LINEAR, CHAR, s8, FLOAT, f32) GO(ARITH_LINEAR, USHORT, u16, FLOAT, f32)
 	GO(ARITH_LINEAR, SHORT, s16, FLOAT, f32) GO(ARITH_LINEAR, UINT, u32, FLOAT, f32) GO(ARITH_LINEAR, INT, s32, FLOAT, f32)
@@ -539,10 +289,10 @@ VH_DEV void stats_block_reduce(const StatsAcc<T> &acc, StatsPartial *dst)
 {
 	typedef typename StatsSums<T>::Sum Sum;
 	typedef typename StatsSums<T>::Sum2 Sum2;
-	__shared__ Sum s_sum[ARITH_THREADS];
-	__shared__ Sum2 s_sum2[ARITH_THREADS];
-	__shared__ T s_mn[ARITH_THREADS], s_mx[ARITH_THREADS];
-	__shared__ unsigned int s_imn[ARITH_THREADS], s_imx[ARITH_THREADS];
+	__shared__ Sum s_sum[POINTWISE_THREADS];
+	__shared__ Sum2 s_sum2[POINTWISE_THREADS];
+	__shared__ T s_mn[POINTWISE_THREADS], s_mx[POINTWISE_THREADS];
+	__shared__ unsigned int s_imn[POINTWISE_THREADS], s_imx[POINTWISE_THREADS];
 	const int t = tid();
 	barrier(); // (the band before this one has been read)
 	s_sum[t] = acc.sum;
@@ -552,7 +302,7 @@ VH_DEV void stats_block_reduce(const StatsAcc<T> &acc, StatsPartial *dst)
 	s_imn[t] = acc.imn;
 	s_imx[t] = acc.imx;
 	barrier();
-	for (int s = ARITH_THREADS / 2; s > 0; s >>= 1) {
+	for (int s = POINTWISE_THREADS / 2; s > 0; s >>= 1) {
 		if (t < s) {
 			const int o = t + s;
 			s_sum[t] += s_sum[o];
@@ -588,16 +338,16 @@ VH_DEV void stats_block_reduce(const StatsAcc<T> &acc, StatsPartial *dst)
 }
 
 template <typename T, int B>
-__global__ void __launch_bounds__(ARITH_THREADS)
+__global__ void __launch_bounds__(POINTWISE_THREADS)
 stats_stream_kernel(StatsArgs a)
 {
-	constexpr int NP = ARITH_GROUP / (int) sizeof(T); // pels a lane takes at a time: B groups of 16 bytes
+	constexpr int NP = POINTWISE_GROUP / (int) sizeof(T); // pels a lane takes at a time: B groups of 16 bytes
 	StatsAcc<T> acc[B];
 #pragma unroll
 	for (int b = 0; b < B; b++)
 		acc[b].clear();
 	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
-	for (unsigned int at = (unsigned int) blockIdx.x * ARITH_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * ARITH_THREADS) {
+	for (unsigned int at = (unsigned int) blockIdx.x * POINTWISE_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * POINTWISE_THREADS) {
 		const int y = (int) (at / (unsigned int) a.groups);
 		const int g = (int) (at - (unsigned int) y * (unsigned int) a.groups);
 		const int p0 = g * NP;
@@ -606,10 +356,10 @@ stats_stream_kernel(StatsArgs a)
 		const unsigned int index = (unsigned int) y * (unsigned int) a.width + (unsigned int) p0;
 		if (n == NP) {
 			unsigned int d[4 * B];
-			arith_load<4 * B>(gptr_in_of(row), (unsigned int) g * (unsigned int) (ARITH_GROUP * B), d);
+			group_load<4 * B>(gptr_in_of(row), (unsigned int) g * (unsigned int) (POINTWISE_GROUP * B), d);
 #pragma unroll
 			for (int j = 0; j < NP * B; j++)
-				acc[j % B].take(arith_take<T, 4 * B>(d, j), index + (unsigned int) (j / B));
+				acc[j % B].take(group_take<T, 4 * B>(d, j), index + (unsigned int) (j / B));
 		}
 		else {
 			for (int j = 0; j < n; j++) {
@@ -625,14 +375,14 @@ stats_stream_kernel(StatsArgs a)
 }
 
 template <typename T>
-__global__ void __launch_bounds__(ARITH_THREADS)
+__global__ void __launch_bounds__(POINTWISE_THREADS)
 stats_general_kernel(StatsArgs a)
 {
 	const int band = (int) blockIdx.y;
 	StatsAcc<T> acc;
 	acc.clear();
 	const unsigned int total = (unsigned int) a.width * (unsigned int) a.height;
-	for (unsigned int at = (unsigned int) blockIdx.x * ARITH_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * ARITH_THREADS) {
+	for (unsigned int at = (unsigned int) blockIdx.x * POINTWISE_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * POINTWISE_THREADS) {
 		const unsigned int y = at / (unsigned int) a.width, x = at - y * (unsigned int) a.width;
 		acc.take(((const T *) (a.in + (long long) y * a.stride))[(long long) x * a.bands + band], at);
 	}
@@ -656,7 +406,7 @@ static bool stats_stream_ok(const _VipsHipImage *in)
 
 static int stats_groups(const _VipsHipImage *in)
 {
-	const int np = ARITH_GROUP / format_sizeof(in->format);
+	const int np = POINTWISE_GROUP / format_sizeof(in->format);
 	return ((stats_joined(in) ? in->width * in->height : in->width) + np - 1) / np;
 }
 
@@ -664,9 +414,9 @@ int stats_blocks(const _VipsHipImage *in)
 {
 	long long blocks;
 	if (stats_stream_ok(in))
-		blocks = ((long long) stats_groups(in) * (stats_joined(in) ? 1 : in->height) + ARITH_THREADS - 1) / ARITH_THREADS;
+		blocks = ((long long) stats_groups(in) * (stats_joined(in) ? 1 : in->height) + POINTWISE_THREADS - 1) / POINTWISE_THREADS;
 	else
-		blocks = ((long long) in->width * in->height + ARITH_THREADS - 1) / ARITH_THREADS;
+		blocks = ((long long) in->width * in->height + POINTWISE_THREADS - 1) / POINTWISE_THREADS;
 	const int cap = stats_stream_ok(in) ? STATS_GRID_BLOCKS : STATS_GRID_BLOCKS / (in->bands < STATS_GRID_BLOCKS ? in->bands : STATS_GRID_BLOCKS);
 	blocks = blocks > cap ? cap : blocks;
 	return (int) (blocks < 1 ? 1 : blocks);
@@ -676,7 +426,7 @@ template <typename T>
 static int stats_launch(const char *domain, const _VipsHipImage *in, StatsArgs a)
 {
 	const int blocks = stats_blocks(in);
-	dim3 block(ARITH_THREADS, 1, 1);
+	dim3 block(POINTWISE_THREADS, 1, 1);
 	if (stats_stream_ok(in)) {
 		a.groups = stats_groups(in);
 		if (stats_joined(in)) {

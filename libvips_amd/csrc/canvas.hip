@@ -26,16 +26,11 @@
 // own double division; four RGBA pels a lane as dwords where rows start on dwords) and flatten_any<T> (the double
 // macros, :88-165).  The file is compiled with -ffp-contract=off: multiply and add stay separate, as in the
 // reference's baseline x86-64 code.
-#include "gcn.h"
-#include "internal.h"
-#include "kernel_stmt.h"
-
-#include <cstdint>
-#include <cstdlib>
+#include "pointwise.h"
 
 namespace vh {
 
-constexpr int CANVAS_THREADS = 256;
+constexpr int CANVAS_THREADS = POINTWISE_THREADS;
 
 constexpr int canvas_group_of(int pel) { return 16 % pel == 0 ? 16 : (48 % pel == 0 ? 48 : 0); }
 
@@ -214,14 +209,6 @@ canvas_stream_kernel(CanvasArgs a)
 
 // ---------------------------------------------------------------- dispatch
 
-static int canvas_rows_grid(int blocks_x, int rows)
-{
-	// enough blocks to fill the part, rows dealt round-robin over grid.y
-	int gy = (256 * 8 + blocks_x - 1) / blocks_x;
-	gy = gy < 1 ? 1 : gy;
-	return gy > rows ? rows : gy;
-}
-
 // the largest of 8, 4, 2, 1 that divides every row start (and the pel size)
 static int canvas_unit(const CanvasArgs &a, int most, bool with_pel)
 {
@@ -239,7 +226,7 @@ static int canvas_unit(const CanvasArgs &a, int most, bool with_pel)
 static void canvas_launch_general(const CanvasArgs &a)
 {
 	const int bx = (a.out_width + CANVAS_THREADS - 1) / CANVAS_THREADS;
-	dim3 grid(bx, canvas_rows_grid(bx, a.out_height), 1), block(CANVAS_THREADS, 1, 1);
+	dim3 grid(bx, pointwise_rows_grid(bx, a.out_height), 1), block(CANVAS_THREADS, 1, 1);
 	Gate gate("canvas_general");
 	switch (canvas_unit(a, 8, true)) {
 	case 8: hipLaunchKernelGGL((canvas_general_kernel<unsigned long long>), grid, block, 0, stream(), a); break;
@@ -255,8 +242,7 @@ static void canvas_launch_stream(CanvasArgs a)
 	constexpr int NP = canvas_group_of(P) / P;
 	a.groups = (a.out_width + NP - 1) / NP;
 	// enough blocks to fill the part (as many as rot.hip's streams launch), the rest of the groups in turns
-	const long long blocks = ((long long) a.groups * a.out_height + CANVAS_THREADS - 1) / CANVAS_THREADS;
-	dim3 grid((unsigned int) (blocks < 256 * 8 ? blocks : 256 * 8), 1, 1), block(CANVAS_THREADS, 1, 1);
+	dim3 grid = pointwise_stream_grid((long long) a.groups * a.out_height), block(CANVAS_THREADS, 1, 1);
 	Gate gate("canvas_stream");
 	hipLaunchKernelGGL((canvas_stream_kernel<P>), grid, block, 0, stream(), a);
 }
@@ -442,7 +428,7 @@ int flatten_run(const char *domain, FlattenArgs a, int format)
 		const bool quad = a.bands == 4 && all % 4 == 0;
 		const int lanes = quad ? (a.width + 3) / 4 : a.width;
 		const int bx = (lanes + FLATTEN_THREADS - 1) / FLATTEN_THREADS;
-		dim3 grid(bx, canvas_rows_grid(bx, a.height), 1);
+		dim3 grid(bx, pointwise_rows_grid(bx, a.height), 1);
 		Gate gate("flatten_u8");
 		if (quad)
 			hipLaunchKernelGGL((flatten_u8_kernel<true>), grid, block, 0, stream(), a);
@@ -452,7 +438,7 @@ int flatten_run(const char *domain, FlattenArgs a, int format)
 		return 0;
 	}
 	const int bx = (a.width + FLATTEN_THREADS - 1) / FLATTEN_THREADS;
-	dim3 grid(bx, canvas_rows_grid(bx, a.height), 1);
+	dim3 grid(bx, pointwise_rows_grid(bx, a.height), 1);
 	Gate gate("flatten_any");
 	switch (format) {
 #define GO(F, T) \
@@ -500,7 +486,7 @@ int addalpha_run(const char *domain, const unsigned char *in, long long in_strid
 		return -1;
 	}
 	const int bx = (width + FLATTEN_THREADS - 1) / FLATTEN_THREADS;
-	dim3 grid(bx, canvas_rows_grid(bx, height), 1), block(FLATTEN_THREADS, 1, 1);
+	dim3 grid(bx, pointwise_rows_grid(bx, height), 1), block(FLATTEN_THREADS, 1, 1);
 	Gate gate("addalpha");
 	switch (es) {
 	case 1: hipLaunchKernelGGL((addalpha_kernel<unsigned char>), grid, block, 0, stream(), in, in_stride, out, out_stride, width, height, bands, alpha); break;

@@ -153,6 +153,30 @@ namespace vh {
 // Run where the data lives: make sure a device is selected and bind the calling thread to the
 // device `image` is on (every image-level operation starts with this).
 int bind_to(const _VipsHipImage *image);
+// A reference to an image that is dropped on the way out of a scope, unless it is released to the caller.
+struct ImageRef {
+	VipsHipImage *im;
+	explicit ImageRef(VipsHipImage *i = nullptr)
+		: im(i)
+	{
+	}
+	~ImageRef() { vips_hip_image_unref(im); }
+	VipsHipImage *release()
+	{
+		VipsHipImage *t = im;
+		im = nullptr;
+		return t;
+	}
+};
+// ... device memory from the pool (nullptr for no bytes, and when the pool fails)
+struct DeviceBlock {
+	void *p;
+	explicit DeviceBlock(size_t size)
+		: p(size ? vips_hip_malloc(size) : nullptr)
+	{
+	}
+	~DeviceBlock() { vips_hip_free(p); }
+};
 // A second image object on the same pixels (library-owned images only; nullptr otherwise).  It has no orientation.
 _VipsHipImage *image_share(const _VipsHipImage *in);
 // rot.hip: out = in turned and / or mirrored in one launch; op is a sum of ROT_OP_*
@@ -317,13 +341,11 @@ int flatten_run(const char *domain, FlattenArgs a, int format);
 // ... vips_addalpha: every pel's `bands` elements of `es` bytes, then `alpha` (the low es bytes)
 int addalpha_run(const char *domain, const unsigned char *in, long long in_stride, unsigned char *out, long long out_stride,
 	int width, int height, int bands, int es, unsigned long long alpha);
-// arith.hip: the pointwise operations of arithmetic/ on checked geometry (ops_arith.cpp checks everything): ONE launch
-// writes `height` rows of `elems` output elements.  Output element e of row y is made from element e of the operand's
-// row, or -- an operand of one element a pel (b1 / b2 == 1) against `bands` -- from element e / bands; an operand is
-// zero right of its w1 / w2 pels and below its h1 / h2 rows (vips__sizealike: embedded black at (0, 0)).
-enum { ARITH_LINEAR = 0, ARITH_INVERT, ARITH_ABS, ARITH_ADD, ARITH_SUBTRACT, ARITH_MULTIPLY, ARITH_DIVIDE, ARITH_LAST };
-constexpr int ARITH_MAX_VECTOR = 32; // elements of vips_linear's a and b once they differ from band to band
-struct ArithArgs {
+// pointwise.h: the geometry of a pointwise launch on checked operands: ONE launch writes `height` rows of `elems` output
+// elements.  Output element e of row y is made from element e of the operand's row, or -- an operand of one element a
+// pel (b1 / b2 == 1) against `bands` -- from element e / bands; an operand is zero right of its w1 / w2 pels and below
+// its h1 / h2 rows (vips__sizealike: embedded black at (0, 0)).
+struct PointwiseGeom {
 	const unsigned char *in;
 	const unsigned char *in2; // the right-hand operand of the binary operations
 	unsigned char *out;
@@ -332,6 +354,24 @@ struct ArithArgs {
 	int bands;                                    // elements a pel of the output
 	int w1, h1, b1, w2, h2, b2;
 	int groups; // (stream kernel) 16-byte groups of an output row, the ragged one included
+};
+// ops_arith.cpp: the geometry of a unary call on a pair of windows, and of a binary call on two images and the output
+void pointwise_unary_geom(const VipsHipRegion *in, const VipsHipRegion *out, PointwiseGeom *g);
+void pointwise_binary_geom(const _VipsHipImage *left, const _VipsHipImage *right, const _VipsHipImage *out, PointwiseGeom *g);
+// ... what a call on two images does between its null checks and its launch: the images are on one device, `plan`
+// (vips_hip_binary_plan, vips_hip_logic_plan) fills the result's header, what is not in the common format is cast
+// (vips__formatalike), the rows are short enough to index, the output is made and `geom` filled
+struct BinaryOperands {
+	int format, out_format, bands, interpretation, width, height;
+	ImageRef cast[2], out;
+	PointwiseGeom geom;
+};
+typedef int (*BinaryPlanFn)(const void *closure, const _VipsHipImage *left, const _VipsHipImage *right, BinaryOperands *b);
+int binary_operands(const char *domain, _VipsHipImage *left, _VipsHipImage *right, BinaryPlanFn plan, const void *closure, BinaryOperands *b);
+// arith.hip: the pointwise operations of arithmetic/ (ops_arith.cpp checks everything)
+enum { ARITH_LINEAR = 0, ARITH_INVERT, ARITH_ABS, ARITH_ADD, ARITH_SUBTRACT, ARITH_MULTIPLY, ARITH_DIVIDE, ARITH_LAST };
+constexpr int ARITH_MAX_VECTOR = 32; // elements of vips_linear's a and b once they differ from band to band
+struct ArithArgs : PointwiseGeom {
 	int single; // vips_linear: every element of a and of b the same (LOOP1, linear.c:213-223)
 	float a1, b1f; // ... those, as the float the reference makes of them
 	double a[ARITH_MAX_VECTOR], b[ARITH_MAX_VECTOR]; // a_ready, b_ready (linear.c:181-200)
@@ -358,24 +398,13 @@ int format_common(int a, int b);
 // ... vips_check_noncomplex's words for a complex format; a pair of windows of the same size, non-complex, not in place
 int arithmetic_noncomplex(const char *domain, int format);
 int arithmetic_window_pair(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out);
-// logic.hip: the comparisons and booleans of arithmetic/relational.c and boolean.c on checked geometry (ops_logic.cpp
-// checks everything), with ArithArgs' conventions: ONE launch writes `height` rows of `elems` output elements; output
-// element e of row y is made from element e of an operand's row, or -- an operand of one element a pel (b1 / b2 == 1)
-// against `bands` -- from element e / bands; an operand is zero right of its w1 / w2 pels and below its h1 / h2 rows.
+// logic.hip: the comparisons and booleans of arithmetic/relational.c and boolean.c (ops_logic.cpp checks everything).
 // in2 == nullptr: the right-hand side is the constants (unaryconst.c:90-120).
 enum { LOGIC_RELATIONAL = 0, LOGIC_BOOLEAN };
 enum { RELATIONAL_EQUAL = 0, RELATIONAL_NOTEQ, RELATIONAL_LESS, RELATIONAL_LESSEQ, RELATIONAL_MORE, RELATIONAL_MOREEQ, RELATIONAL_LAST };
 enum { BOOLEAN_AND = 0, BOOLEAN_OR, BOOLEAN_EOR, BOOLEAN_LSHIFT, BOOLEAN_RSHIFT, BOOLEAN_LAST };
 constexpr int LOGIC_MAX_VECTOR = 32; // constants once they differ from band to band
-struct LogicArgs {
-	const unsigned char *in;
-	const unsigned char *in2;
-	unsigned char *out;
-	long long in_stride, in2_stride, out_stride; // bytes
-	int elems, height;                            // of the output
-	int bands;                                    // elements a pel of the output
-	int w1, h1, b1, w2, h2, b2;
-	int groups; // (stream kernel) 16-byte groups of an output row, the ragged one included
+struct LogicArgs : PointwiseGeom {
 	int single; // every constant the same
 	int is_int; // relational_const compares with c_int (relational.c:528-529)
 	int c_int[LOGIC_MAX_VECTOR];

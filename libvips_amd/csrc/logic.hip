@@ -3,14 +3,9 @@
 // vips_bandjoin_const / vips_extract_band / vips_bandmean / vips_bandbool (conversion/bandjoin.c, extract.c, bandmean.c,
 // bandbool.c) on the device (gfx950).  Every operation is ONE launch that writes every output byte once.
 //
-//   logic_stream<FAMILY, OP, CONST, IN>   the comparisons and booleans, with arith.hip's skeleton (instantiated here, so
-//                               that arith.hip's code objects stay what they were): lanes on consecutive 16-byte groups
-//                               of an OUTPUT row, the operands' 16 .. 128 bytes read as aligned dwords, one
-//                               global_store_dwordx4; a row's ragged last group element by element inside the same
-//                               launch; per-band constants in LDS, picked by (element index) mod bands.
-//   logic_general<...>          one element a lane: defines correctness and takes what the stream declines -- rows off
-//                               dwords, a one-band operand against n bands (by pel), operands of different sizes (zero
-//                               outside an operand's rectangle) -- and everything under VIPS_HIP_NO_LOGIC_STREAM.
+//   logic_stream, logic_general   the comparisons and booleans through pointwise.h's two kernels: this file gives them
+//                               the expressions (logic_elem) and the policy (LogicOp: the constants of the *_const
+//                               operations are staged to LDS); everything under VIPS_HIP_NO_LOGIC_STREAM is general.
 //   select_stream<T, BLEND, B>  three operands.  B == 0: the condition has the operands' bands, a lane makes one 16-byte
 //                               group and reads the matching 16 / sizeof(T) condition bytes.  B == 2 .. 4: a ONE-band
 //                               condition over B-band operands (a mask over RGB): a lane makes B consecutive groups --
@@ -32,29 +27,9 @@
 //
 // The arithmetic is the reference's, expression by expression (cited in place); the file is compiled with
 // -ffp-contract=off, float -> int conversions are v_cvt_i32 by name (vh::cvt_i32).
-#include "gcn.h"
-#include "internal.h"
-#include "kernel_stmt.h"
-
-#include <cstdint>
-#include <cstdlib>
-#include <type_traits>
+#include "pointwise.h"
 
 namespace vh {
-
-constexpr int LOGIC_THREADS = 256;
-constexpr int LOGIC_GROUP = 16;            // bytes of the output a lane makes at a time
-constexpr int LOGIC_GRID_BLOCKS = 256 * 8; // of a stream launch (as arith_stream)
-
-typedef unsigned char u8;
-typedef signed char s8;
-typedef unsigned short u16;
-typedef short s16;
-typedef unsigned int u32;
-typedef int s32;
-typedef float f32;
-typedef double f64;
-typedef unsigned long long u64;
 
 // ---------------------------------------------------------------- the reference's expressions
 
@@ -223,54 +198,6 @@ VH_DEV u32 band_fold(u32 acc, u32 v)
 
 // ---------------------------------------------------------------- registers <-> elements
 
-// element i (a constant once the loops are unrolled) of the dwords of a group
-template <typename T, int ND>
-VH_DEV T logic_take(const unsigned int (&d)[ND], int i)
-{
-	if constexpr (sizeof(T) == 1)
-		return (T) (d[i >> 2] >> (8 * (i & 3)));
-	else if constexpr (sizeof(T) == 2)
-		return (T) (d[i >> 1] >> (16 * (i & 1)));
-	else if constexpr (sizeof(T) == 4)
-		return __builtin_bit_cast(T, d[i]);
-	else
-		return __builtin_bit_cast(T, (u64) d[2 * i] | ((u64) d[2 * i + 1] << 32));
-}
-
-template <typename T>
-VH_DEV void logic_put(unsigned int (&w)[4], int i, T v)
-{
-	if constexpr (sizeof(T) == 1)
-		w[i >> 2] |= (unsigned int) (u8) v << (8 * (i & 3));
-	else if constexpr (sizeof(T) == 2)
-		w[i >> 1] |= (unsigned int) (u16) v << (16 * (i & 1));
-	else if constexpr (sizeof(T) == 4)
-		w[i] = __builtin_bit_cast(unsigned int, v);
-	else {
-		const u64 bits = __builtin_bit_cast(u64, v);
-		w[2 * i] = (unsigned int) bits;
-		w[2 * i + 1] = (unsigned int) (bits >> 32);
-	}
-}
-
-// ND dwords (1, 2 or a multiple of 4) at a dword-aligned offset
-template <int ND>
-VH_DEV void logic_load(gptr_in base, unsigned int off, unsigned int (&d)[ND])
-{
-	if constexpr (ND < 4)
-		gload_dwords<ND>(base, off, d);
-	else {
-#pragma unroll
-		for (int q = 0; q < ND / 4; q++) {
-			unsigned int t[4];
-			gload128(base, off + 16u * (unsigned int) q, t);
-#pragma unroll
-			for (int i = 0; i < 4; i++)
-				d[4 * q + i] = t[i];
-		}
-	}
-}
-
 // NB bytes (2, 4, 8 or 16) at an offset that is a multiple of NB (of 4 for 8 and 16), the rest of d zero
 template <int NB>
 VH_DEV void logic_load_bytes(gptr_in base, unsigned int off, unsigned int (&d)[4])
@@ -309,112 +236,21 @@ VH_DEV void logic_constants(const LogicArgs &a, int *ci, double *cd)
 	barrier();
 }
 
-// ---------------------------------------------------------------- comparisons and booleans: one element a lane
+// ---------------------------------------------------------------- comparisons and booleans: the policy
 
-template <int FAMILY, int OP, bool CONST, typename IN>
-__global__ void __launch_bounds__(LOGIC_THREADS)
-logic_general_kernel(LogicArgs a)
-{
+template <int FAMILY, int OP, bool CONST, typename IN_>
+struct LogicOp {
+	typedef IN_ IN;
 	typedef typename LogicOut<FAMILY, IN>::type OUT;
-	__shared__ int ci[LOGIC_MAX_VECTOR];
-	__shared__ double cd[LOGIC_MAX_VECTOR];
-	if constexpr (CONST)
-		logic_constants(a, ci, cd);
-	const int e = (int) blockIdx.x * LOGIC_THREADS + (int) threadIdx.x;
-	if (e >= a.elems)
-		return;
-	const int pel = e / a.bands, k = e - pel * a.bands;
-	const int i1 = a.b1 == 1 ? pel : e, i2 = a.b2 == 1 ? pel : e;
-	int ck = 0;
-	double dk = 0.0;
-	if constexpr (CONST) {
-		ck = ci[a.single ? 0 : k];
-		dk = cd[a.single ? 0 : k];
-	}
-	for (int y = (int) blockIdx.y; y < a.height; y += (int) gridDim.y) {
-		IN l = (IN) 0, r = (IN) 0;
-		if (pel < a.w1 && y < a.h1)
-			l = ((const IN *) (a.in + (long long) y * a.in_stride))[i1];
-		if constexpr (!CONST)
-			if (pel < a.w2 && y < a.h2)
-				r = ((const IN *) (a.in2 + (long long) y * a.in2_stride))[i2];
-		((OUT *) (a.out + (long long) y * a.out_stride))[e] = logic_elem<FAMILY, OP, CONST, IN>(l, r, a.is_int != 0, ck, dk);
-	}
-}
-
-// ---------------------------------------------------------------- ... 16 bytes of the output a lane
-
-template <int FAMILY, int OP, bool CONST, typename IN>
-__global__ void __launch_bounds__(LOGIC_THREADS)
-logic_stream_kernel(LogicArgs a)
-{
-	typedef typename LogicOut<FAMILY, IN>::type OUT;
-	constexpr int NE = LOGIC_GROUP / (int) sizeof(OUT);
-	constexpr int ND = NE * (int) sizeof(IN) / 4; // dwords of an operand's group
-	__shared__ int ci[LOGIC_MAX_VECTOR];
-	__shared__ double cd[LOGIC_MAX_VECTOR];
-	if constexpr (CONST)
-		logic_constants(a, ci, cd);
-	const bool vector = CONST && !a.single;
-	int c0 = 0;
-	double d0 = 0.0;
-	if constexpr (CONST) {
-		c0 = ci[0];
-		d0 = cd[0];
-	}
-	const bool is_int = a.is_int != 0;
-	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
-	for (unsigned int at = (unsigned int) blockIdx.x * LOGIC_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * LOGIC_THREADS) {
-		const int y = (int) (at / (unsigned int) a.groups);
-		const int g = (int) (at - (unsigned int) y * (unsigned int) a.groups);
-		const int e0 = g * NE;
-		const int n = min(NE, a.elems - e0); // < NE: the row's ragged end
-		const unsigned long long irow = (unsigned long long) a.in + (unsigned long long) y * a.in_stride;
-		const unsigned long long irow2 = (unsigned long long) a.in2 + (unsigned long long) y * a.in2_stride;
-		const unsigned long long orow = (unsigned long long) a.out + (unsigned long long) y * a.out_stride;
-		int k = vector ? e0 % a.bands : 0;
-		if (n == NE) {
-			unsigned int d[ND], d2[ND], w[4] = { 0, 0, 0, 0 };
-			logic_load<ND>(gptr_in_of(irow), (unsigned int) e0 * (unsigned int) sizeof(IN), d);
-			if constexpr (!CONST)
-				logic_load<ND>(gptr_in_of(irow2), (unsigned int) e0 * (unsigned int) sizeof(IN), d2);
-#pragma unroll
-			for (int i = 0; i < NE; i++) {
-				const IN l = logic_take<IN, ND>(d, i);
-				IN r = (IN) 0;
-				if constexpr (!CONST)
-					r = logic_take<IN, ND>(d2, i);
-				int ck = c0;
-				double dk = d0;
-				if constexpr (CONST)
-					if (vector) {
-						ck = ci[k];
-						dk = cd[k];
-						k = k + 1 == a.bands ? 0 : k + 1;
-					}
-				logic_put<OUT>(w, i, logic_elem<FAMILY, OP, CONST, IN>(l, r, is_int, ck, dk));
-			}
-			gstore128(gptr_out_of(orow) + (unsigned int) g * LOGIC_GROUP, w);
-		}
-		else {
-			for (int i = 0; i < n; i++) {
-				const IN l = ((const IN *) irow)[e0 + i];
-				IN r = (IN) 0;
-				if constexpr (!CONST)
-					r = ((const IN *) irow2)[e0 + i];
-				int ck = c0;
-				double dk = d0;
-				if constexpr (CONST)
-					if (vector) {
-						ck = ci[k];
-						dk = cd[k];
-						k = k + 1 == a.bands ? 0 : k + 1;
-					}
-				((OUT *) orow)[e0 + i] = logic_elem<FAMILY, OP, CONST, IN>(l, r, is_int, ck, dk);
-			}
-		}
-	}
-}
+	typedef LogicArgs Args;
+	typedef int CA;
+	typedef double CB;
+	static constexpr int MAX_VECTOR = LOGIC_MAX_VECTOR;
+	static constexpr bool binary = !CONST;
+	static constexpr bool constants = CONST;
+	VH_DEV void stage(const LogicArgs &a, int *ci, double *cd) { logic_constants(a, ci, cd); }
+	VH_DEV OUT elem(const LogicArgs &a, IN l, IN r, int ck, double dk) { return logic_elem<FAMILY, OP, CONST, IN>(l, r, a.is_int != 0, ck, dk); }
+};
 
 // ---------------------------------------------------------------- select: one element a lane
 
@@ -428,10 +264,10 @@ VH_DEV T select_elem(u8 c, T t, T f)
 }
 
 template <typename T, bool BLEND>
-__global__ void __launch_bounds__(LOGIC_THREADS)
+__global__ void __launch_bounds__(POINTWISE_THREADS)
 select_general_kernel(SelectArgs a)
 {
-	const int e = (int) blockIdx.x * LOGIC_THREADS + (int) threadIdx.x;
+	const int e = (int) blockIdx.x * POINTWISE_THREADS + (int) threadIdx.x;
 	if (e >= a.elems)
 		return;
 	const int pel = e / a.bands;
@@ -462,14 +298,14 @@ VH_DEV u8 logic_byte_at(const unsigned int (&c)[4], int idx)
 // one-band condition over any number of bands -- a.bands groups a unit, the loop over them is not unrolled and the
 // element's condition byte is picked by its run-time pel index
 template <typename T, bool BLEND, int B>
-__global__ void __launch_bounds__(LOGIC_THREADS)
+__global__ void __launch_bounds__(POINTWISE_THREADS)
 select_stream_kernel(SelectArgs a)
 {
-	constexpr int NE = LOGIC_GROUP / (int) sizeof(T); // elements of a group; pels of a unit where B != 0
+	constexpr int NE = POINTWISE_GROUP / (int) sizeof(T); // elements of a group; pels of a unit where B != 0
 	if constexpr (B < 0) {
 		const int ng = a.bands;
 		const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
-		for (unsigned int at = (unsigned int) blockIdx.x * LOGIC_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * LOGIC_THREADS) {
+		for (unsigned int at = (unsigned int) blockIdx.x * POINTWISE_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * POINTWISE_THREADS) {
 			const int y = (int) (at / (unsigned int) a.groups);
 			const int u = (int) (at - (unsigned int) y * (unsigned int) a.groups);
 			const int e0 = u * NE * ng;
@@ -484,13 +320,13 @@ select_stream_kernel(SelectArgs a)
 				int pel = 0, k = 0; // of the next element: its pel in the unit, its band in the pel
 				for (int j = 0; j < ng; j++) {
 					unsigned int d[4], d2[4], w[4] = { 0, 0, 0, 0 };
-					const unsigned int off = (unsigned int) e0 * (unsigned int) sizeof(T) + (unsigned int) j * LOGIC_GROUP;
+					const unsigned int off = (unsigned int) e0 * (unsigned int) sizeof(T) + (unsigned int) j * POINTWISE_GROUP;
 					gload128(gptr_in_of(irow), off, d);
 					gload128(gptr_in_of(irow2), off, d2);
 #pragma unroll
 					for (int i = 0; i < NE; i++) {
 						const u8 cv = logic_byte_at(c, pel);
-						logic_put<T>(w, i, select_elem<T, BLEND>(cv, logic_take<T, 4>(d, i), logic_take<T, 4>(d2, i)));
+						group_put<T>(w, i, select_elem<T, BLEND>(cv, group_take<T, 4>(d, i), group_take<T, 4>(d2, i)));
 						k++;
 						if (k == ng) {
 							k = 0;
@@ -511,7 +347,7 @@ select_stream_kernel(SelectArgs a)
 	}
 	constexpr int NG = B > 0 ? B : 1;
 	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
-	for (unsigned int at = (unsigned int) blockIdx.x * LOGIC_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * LOGIC_THREADS) {
+	for (unsigned int at = (unsigned int) blockIdx.x * POINTWISE_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * POINTWISE_THREADS) {
 		const int y = (int) (at / (unsigned int) a.groups);
 		const int u = (int) (at - (unsigned int) y * (unsigned int) a.groups);
 		const int e0 = u * NE * NG;
@@ -527,13 +363,13 @@ select_stream_kernel(SelectArgs a)
 #pragma unroll
 			for (int j = 0; j < NG; j++) {
 				unsigned int d[4], d2[4], w[4] = { 0, 0, 0, 0 };
-				const unsigned int off = (unsigned int) e0 * (unsigned int) sizeof(T) + (unsigned int) j * LOGIC_GROUP;
+				const unsigned int off = (unsigned int) e0 * (unsigned int) sizeof(T) + (unsigned int) j * POINTWISE_GROUP;
 				gload128(gptr_in_of(irow), off, d);
 				gload128(gptr_in_of(irow2), off, d2);
 #pragma unroll
 				for (int i = 0; i < NE; i++) {
-					const u8 cv = logic_take<u8, 4>(c, B ? (j * NE + i) / NG : i);
-					logic_put<T>(w, i, select_elem<T, BLEND>(cv, logic_take<T, 4>(d, i), logic_take<T, 4>(d2, i)));
+					const u8 cv = group_take<u8, 4>(c, B ? (j * NE + i) / NG : i);
+					group_put<T>(w, i, select_elem<T, BLEND>(cv, group_take<T, 4>(d, i), group_take<T, 4>(d2, i)));
 				}
 				gstore128(gptr_out_of(orow) + off, w);
 			}
@@ -604,13 +440,13 @@ VH_DEV typename BandOut<T, OP>::type band_reduce(const T *p, int bands)
 }
 
 template <typename T, int OP>
-__global__ void __launch_bounds__(LOGIC_THREADS)
+__global__ void __launch_bounds__(POINTWISE_THREADS)
 band_general_kernel(BandArgs a)
 {
 	typedef typename BandOut<T, OP>::type OUT;
 	__shared__ BandSource src[BAND_MAX_SOURCES];
 	band_sources(a, src);
-	const int e = (int) blockIdx.x * LOGIC_THREADS + (int) threadIdx.x;
+	const int e = (int) blockIdx.x * POINTWISE_THREADS + (int) threadIdx.x;
 	if (e >= a.elems)
 		return;
 	const int pel = e / a.out_bands, z = e - pel * a.out_bands;
@@ -624,15 +460,15 @@ band_general_kernel(BandArgs a)
 }
 
 template <typename T, int OP, int B>
-__global__ void __launch_bounds__(LOGIC_THREADS)
+__global__ void __launch_bounds__(POINTWISE_THREADS)
 band_stream_kernel(BandArgs a)
 {
 	typedef typename BandOut<T, OP>::type OUT;
-	constexpr int NE = LOGIC_GROUP / (int) sizeof(OUT);
+	constexpr int NE = POINTWISE_GROUP / (int) sizeof(OUT);
 	__shared__ BandSource src[BAND_MAX_SOURCES];
 	band_sources(a, src);
 	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
-	for (unsigned int at = (unsigned int) blockIdx.x * LOGIC_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * LOGIC_THREADS) {
+	for (unsigned int at = (unsigned int) blockIdx.x * POINTWISE_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * POINTWISE_THREADS) {
 		const int y = (int) (at / (unsigned int) a.groups);
 		const int g = (int) (at - (unsigned int) y * (unsigned int) a.groups);
 		const int e0 = g * NE;
@@ -646,7 +482,7 @@ band_stream_kernel(BandArgs a)
 				if (i < n) {
 					const T v = band_gather<T>(src, a.n, pel, z, y);
 					if (n == NE)
-						logic_put<T>(w, i, v);
+						group_put<T>(w, i, v);
 					else
 						((T *) orow)[e0 + i] = v;
 				}
@@ -657,7 +493,7 @@ band_stream_kernel(BandArgs a)
 				}
 			}
 			if (n == NE)
-				gstore128(gptr_out_of(orow) + (unsigned int) g * LOGIC_GROUP, w);
+				gstore128(gptr_out_of(orow) + (unsigned int) g * POINTWISE_GROUP, w);
 		}
 		else {
 			const unsigned long long irow = (unsigned long long) src[0].in + (unsigned long long) y * src[0].stride;
@@ -667,32 +503,32 @@ band_stream_kernel(BandArgs a)
 				constexpr int NB = B > 0 ? B : 1;
 				constexpr int ND = NB * NE * (int) sizeof(T) / 4;
 				unsigned int d[ND], w[4] = { 0, 0, 0, 0 };
-				logic_load<ND>(gptr_in_of(irow), (unsigned int) e0 * (unsigned int) (NB * sizeof(T)), d);
+				group_load<ND>(gptr_in_of(irow), (unsigned int) e0 * (unsigned int) (NB * sizeof(T)), d);
 #pragma unroll
 				for (int i = 0; i < NE; i++) {
 					if constexpr (OP == BAND_MEAN) {
 						typename BandSum<T>::type sum = 0;
 #pragma unroll
 						for (int j = 0; j < NB; j++)
-							sum += logic_take<T, ND>(d, i * NB + j);
-						logic_put<OUT>(w, i, band_mean<T>(sum, NB));
+							sum += group_take<T, ND>(d, i * NB + j);
+						group_put<OUT>(w, i, band_mean<T>(sum, NB));
 					}
 					else {
-						u32 acc = band_bits<T>(logic_take<T, ND>(d, i * NB));
+						u32 acc = band_bits<T>(group_take<T, ND>(d, i * NB));
 #pragma unroll
 						for (int j = 1; j < NB; j++)
-							acc = band_fold<OP>(acc, band_bits<T>(logic_take<T, ND>(d, i * NB + j)));
-						logic_put<OUT>(w, i, (OUT) acc);
+							acc = band_fold<OP>(acc, band_bits<T>(group_take<T, ND>(d, i * NB + j)));
+						group_put<OUT>(w, i, (OUT) acc);
 					}
 				}
-				gstore128(gptr_out_of(orow) + (unsigned int) g * LOGIC_GROUP, w);
+				gstore128(gptr_out_of(orow) + (unsigned int) g * POINTWISE_GROUP, w);
 			}
 			else if (n == NE) {
 				unsigned int w[4] = { 0, 0, 0, 0 };
 #pragma unroll
 				for (int i = 0; i < NE; i++)
-					logic_put<OUT>(w, i, band_reduce<T, OP>((const T *) irow + (long long) (e0 + i) * src[0].pel_elems, src[0].pel_elems));
-				gstore128(gptr_out_of(orow) + (unsigned int) g * LOGIC_GROUP, w);
+					group_put<OUT>(w, i, band_reduce<T, OP>((const T *) irow + (long long) (e0 + i) * src[0].pel_elems, src[0].pel_elems));
+				gstore128(gptr_out_of(orow) + (unsigned int) g * POINTWISE_GROUP, w);
 			}
 			else {
 				for (int i = 0; i < n; i++)
@@ -710,10 +546,10 @@ band_stream_kernel(BandArgs a)
 // PA * 16 (and NB * 16) contiguous bytes of those pels as aligned dwords and stores NA + NB groups of 16 bytes; which
 // register an output element comes from is a constant.  A row's ragged last unit goes through band_gather.
 template <typename T, int PA, int FA, int NA, int NB, bool CONSTS>
-__global__ void __launch_bounds__(LOGIC_THREADS)
+__global__ void __launch_bounds__(POINTWISE_THREADS)
 band_pels_kernel(BandArgs a)
 {
-	constexpr int NE = LOGIC_GROUP / (int) sizeof(T);
+	constexpr int NE = POINTWISE_GROUP / (int) sizeof(T);
 	constexpr int NO = NA + NB;
 	constexpr int NB1 = NB > 0 ? NB : 1;
 	__shared__ BandSource src[BAND_MAX_SOURCES];
@@ -726,7 +562,7 @@ band_pels_kernel(BandArgs a)
 	const unsigned long long in0 = (unsigned long long) src[0].in, in1 = (unsigned long long) src[NB > 0 && !CONSTS ? 1 : 0].in;
 	const long long stride0 = src[0].stride, stride1 = src[NB > 0 && !CONSTS ? 1 : 0].stride;
 	const unsigned int total = (unsigned int) a.groups * (unsigned int) a.height;
-	for (unsigned int at = (unsigned int) blockIdx.x * LOGIC_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * LOGIC_THREADS) {
+	for (unsigned int at = (unsigned int) blockIdx.x * POINTWISE_THREADS + (unsigned int) threadIdx.x; at < total; at += (unsigned int) gridDim.x * POINTWISE_THREADS) {
 		const int y = (int) (at / (unsigned int) a.groups);
 		const int u = (int) (at - (unsigned int) y * (unsigned int) a.groups);
 		const int p0 = u * NE;
@@ -734,9 +570,9 @@ band_pels_kernel(BandArgs a)
 		const unsigned long long orow = (unsigned long long) a.out + (unsigned long long) y * a.out_stride;
 		if (n == NE) {
 			unsigned int d0[4 * PA], d1[4 * NB1];
-			logic_load<4 * PA>(gptr_in_of(in0 + (unsigned long long) y * stride0), (unsigned int) u * (unsigned int) (LOGIC_GROUP * PA), d0);
+			group_load<4 * PA>(gptr_in_of(in0 + (unsigned long long) y * stride0), (unsigned int) u * (unsigned int) (POINTWISE_GROUP * PA), d0);
 			if constexpr (NB > 0 && !CONSTS)
-				logic_load<4 * NB1>(gptr_in_of(in1 + (unsigned long long) y * stride1), (unsigned int) u * (unsigned int) (LOGIC_GROUP * NB1), d1);
+				group_load<4 * NB1>(gptr_in_of(in1 + (unsigned long long) y * stride1), (unsigned int) u * (unsigned int) (POINTWISE_GROUP * NB1), d1);
 #pragma unroll
 			for (int j = 0; j < NO; j++) {
 				unsigned int w[4] = { 0, 0, 0, 0 };
@@ -745,14 +581,14 @@ band_pels_kernel(BandArgs a)
 					const int flat = j * NE + i, pel = flat / NO, z = flat % NO;
 					T v;
 					if (z < NA)
-						v = logic_take<T, 4 * PA>(d0, pel * PA + FA + z);
+						v = group_take<T, 4 * PA>(d0, pel * PA + FA + z);
 					else if constexpr (CONSTS)
 						v = cv[z - NA < NB1 ? z - NA : 0];
 					else
-						v = logic_take<T, 4 * NB1>(d1, pel * NB1 + (z - NA < NB1 ? z - NA : 0));
-					logic_put<T>(w, i, v);
+						v = group_take<T, 4 * NB1>(d1, pel * NB1 + (z - NA < NB1 ? z - NA : 0));
+					group_put<T>(w, i, v);
 				}
-				gstore128(gptr_out_of(orow) + ((unsigned int) u * NO + (unsigned int) j) * LOGIC_GROUP, w);
+				gstore128(gptr_out_of(orow) + ((unsigned int) u * NO + (unsigned int) j) * POINTWISE_GROUP, w);
 			}
 		}
 		else {
@@ -769,89 +605,10 @@ static bool logic_no_stream()
 	return getenv("VIPS_HIP_NO_LOGIC_STREAM") != nullptr;
 }
 
-static int logic_rows_grid(int blocks_x, int rows)
-{
-	// enough blocks to fill the part, rows dealt round-robin over grid.y
-	int gy = (LOGIC_GRID_BLOCKS + blocks_x - 1) / blocks_x;
-	gy = gy < 1 ? 1 : gy;
-	return gy > rows ? rows : gy;
-}
-
-static dim3 logic_stream_grid(long long units)
-{
-	const long long blocks = (units + LOGIC_THREADS - 1) / LOGIC_THREADS;
-	return dim3((unsigned int) (blocks < LOGIC_GRID_BLOCKS ? blocks : LOGIC_GRID_BLOCKS), 1, 1);
-}
-
-static bool on_unit(const void *p, long long stride, uintptr_t unit)
-{
-	return ((uintptr_t) p | (uintptr_t) stride) % unit == 0;
-}
-
-// every operand as wide, as tall and of as many bands as the output: element e of a row is element e of every side
-static bool logic_same_shape(const LogicArgs &a, bool binary)
-{
-	const int width = a.elems / a.bands;
-	if (a.b1 != a.bands || a.w1 < width || a.h1 < a.height)
-		return false;
-	return !binary || (a.b2 == a.bands && a.w2 >= width && a.h2 >= a.height);
-}
-
-// Rows that follow one another without a gap on every side are one long row (arith_join_rows): it starts on a multiple
-// of `bands` elements wherever a row did, so the band of an element does not change.
-static void logic_join_rows(LogicArgs &a, bool binary, int in_es, int out_es)
-{
-	const long long elems = (long long) a.elems * a.height;
-	// (one row is nothing away from a next one: its stride must not count in the alignment)
-	if (a.height == 1)
-		a.in_stride = a.in2_stride = a.out_stride = 0;
-	if (a.height > 1 && a.in_stride == (long long) a.elems * in_es && a.out_stride == (long long) a.elems * out_es &&
-		(!binary || a.in2_stride == a.in_stride) && a.w1 == a.elems / a.bands && (!binary || a.w2 == a.w1) &&
-		elems * (in_es > out_es ? in_es : out_es) < (1LL << 31)) {
-		a.elems = (int) elems;
-		a.w1 = a.w2 = a.elems / a.bands;
-		a.h1 = a.h2 = a.height = 1;
-		a.in_stride = a.in2_stride = a.out_stride = 0;
-	}
-}
-
 template <int FAMILY, int OP, bool CONST, typename IN>
-static int logic_launch(const char *domain, LogicArgs a)
+static int logic_launch(const char *domain, const LogicArgs &a)
 {
-	typedef typename LogicOut<FAMILY, IN>::type OUT;
-	constexpr bool binary = !CONST;
-	if (!on_unit(a.in, a.in_stride, sizeof(IN)) || (binary && !on_unit(a.in2, a.in2_stride, sizeof(IN))) ||
-		!on_unit(a.out, a.out_stride, sizeof(OUT))) {
-		error(domain, "rows must start on whole elements");
-		return -1;
-	}
-	dim3 block(LOGIC_THREADS, 1, 1);
-	bool streams = !logic_no_stream() && logic_same_shape(a, binary);
-	if (streams) {
-		LogicArgs joined = a;
-		logic_join_rows(joined, binary, (int) sizeof(IN), (int) sizeof(OUT));
-		constexpr int NE = LOGIC_GROUP / (int) sizeof(OUT);
-		const long long groups = ((long long) joined.elems + NE - 1) / NE;
-		// rows that start on dwords on every side; the kernel numbers the groups in 32 bits
-		streams = on_unit(joined.in, joined.in_stride, 4) && (!binary || on_unit(joined.in2, joined.in2_stride, 4)) &&
-			on_unit(joined.out, joined.out_stride, 4) && groups * joined.height < (1LL << 31);
-		if (streams) {
-			a = joined;
-			a.groups = (int) groups;
-		}
-	}
-	if (streams) {
-		Gate gate("logic_stream");
-		hipLaunchKernelGGL((logic_stream_kernel<FAMILY, OP, CONST, IN>), logic_stream_grid((long long) a.groups * a.height), block, 0, stream(), a);
-	}
-	else {
-		const int bx = (a.elems + LOGIC_THREADS - 1) / LOGIC_THREADS;
-		dim3 grid(bx, logic_rows_grid(bx, a.height), 1);
-		Gate gate("logic_general");
-		hipLaunchKernelGGL((logic_general_kernel<FAMILY, OP, CONST, IN>), grid, block, 0, stream(), a);
-	}
-	VH_CHECK(hipGetLastError());
-	return 0;
+	return pointwise_launch<LogicOp<FAMILY, OP, CONST, IN>>(domain, a, "logic_stream", "logic_general", "VIPS_HIP_NO_LOGIC_STREAM");
 }
 
 template <int FAMILY, int OP, bool CONST>
@@ -942,7 +699,7 @@ template <typename T, bool BLEND, int B>
 static void select_stream_launch(const SelectArgs &a)
 {
 	Gate gate("logic_select_stream");
-	hipLaunchKernelGGL((select_stream_kernel<T, BLEND, B>), logic_stream_grid((long long) a.groups * a.height), dim3(LOGIC_THREADS, 1, 1), 0,
+	hipLaunchKernelGGL((select_stream_kernel<T, BLEND, B>), pointwise_stream_grid((long long) a.groups * a.height), dim3(POINTWISE_THREADS, 1, 1), 0,
 		stream(), a);
 }
 
@@ -953,7 +710,7 @@ static int select_launch(const char *domain, SelectArgs a)
 		error(domain, "rows must start on whole elements");
 		return -1;
 	}
-	constexpr int NE = LOGIC_GROUP / (int) sizeof(T);
+	constexpr int NE = POINTWISE_GROUP / (int) sizeof(T);
 	// a one-band condition over n bands: units of NE pels, n groups (2 .. 4: unrolled); the same bands (one band over
 	// one included): of one group
 	const int per_unit = a.bc == a.bands ? 1 : a.bands;
@@ -962,7 +719,7 @@ static int select_launch(const char *domain, SelectArgs a)
 		SelectArgs j = a;
 		const int width = a.elems / a.bands;
 		const long long elems = (long long) a.elems * a.height;
-		// rows that follow one another without a gap on every side are one long row (as logic_join_rows)
+		// rows that follow one another without a gap on every side are one long row (as pointwise_join_rows)
 		if (a.height == 1)
 			j.in_stride = j.in2_stride = j.out_stride = j.cond_stride = 0;
 		if (a.height > 1 && a.in_stride == (long long) a.elems * (int) sizeof(T) && a.in2_stride == a.in_stride && a.out_stride == a.in_stride &&
@@ -991,10 +748,10 @@ static int select_launch(const char *domain, SelectArgs a)
 		}
 	}
 	else {
-		const int bx = (a.elems + LOGIC_THREADS - 1) / LOGIC_THREADS;
-		dim3 grid(bx, logic_rows_grid(bx, a.height), 1);
+		const int bx = (a.elems + POINTWISE_THREADS - 1) / POINTWISE_THREADS;
+		dim3 grid(bx, pointwise_rows_grid(bx, a.height), 1);
 		Gate gate("logic_select_general");
-		hipLaunchKernelGGL((select_general_kernel<T, BLEND>), grid, dim3(LOGIC_THREADS, 1, 1), 0, stream(), a);
+		hipLaunchKernelGGL((select_general_kernel<T, BLEND>), grid, dim3(POINTWISE_THREADS, 1, 1), 0, stream(), a);
 	}
 	VH_CHECK(hipGetLastError());
 	return 0;
@@ -1043,7 +800,7 @@ template <typename T, int OP, int B>
 static void band_stream_launch(const BandArgs &a)
 {
 	Gate gate("logic_band_stream");
-	hipLaunchKernelGGL((band_stream_kernel<T, OP, B>), logic_stream_grid((long long) a.groups * a.height), dim3(LOGIC_THREADS, 1, 1), 0, stream(),
+	hipLaunchKernelGGL((band_stream_kernel<T, OP, B>), pointwise_stream_grid((long long) a.groups * a.height), dim3(POINTWISE_THREADS, 1, 1), 0, stream(),
 		a);
 }
 
@@ -1051,7 +808,7 @@ template <typename T, int PA, int FA, int NA, int NB, bool CONSTS>
 static void band_pels_launch(const BandArgs &a)
 {
 	Gate gate("logic_band_pels");
-	hipLaunchKernelGGL((band_pels_kernel<T, PA, FA, NA, NB, CONSTS>), logic_stream_grid((long long) a.groups * a.height), dim3(LOGIC_THREADS, 1, 1),
+	hipLaunchKernelGGL((band_pels_kernel<T, PA, FA, NA, NB, CONSTS>), pointwise_stream_grid((long long) a.groups * a.height), dim3(POINTWISE_THREADS, 1, 1),
 		0, stream(), a);
 }
 
@@ -1061,7 +818,7 @@ static void band_pels_launch(const BandArgs &a)
 template <typename T>
 static bool band_pels_takes(BandArgs &a)
 {
-	constexpr int NE = LOGIC_GROUP / (int) sizeof(T);
+	constexpr int NE = POINTWISE_GROUP / (int) sizeof(T);
 	const int width = a.elems / a.out_bands;
 	const BandSource &s0 = a.src[0];
 	int images = 0;
@@ -1114,11 +871,11 @@ static int band_launch(const char *domain, BandArgs a)
 			error(domain, "rows must start on whole elements");
 			return -1;
 		}
-	constexpr int NE = LOGIC_GROUP / (int) sizeof(OUT);
+	constexpr int NE = POINTWISE_GROUP / (int) sizeof(OUT);
 	bool streams = !logic_no_stream();
 	if (streams) {
 		// rows that follow one another without a gap on every side are one long row of width * height pels (as
-		// logic_join_rows; the pels stay whole)
+		// pointwise_join_rows; the pels stay whole)
 		BandArgs j = a;
 		const int width = a.elems / a.out_bands;
 		bool gapless = a.height > 1 && a.out_stride == (long long) a.elems * (int) sizeof(OUT);
@@ -1163,10 +920,10 @@ static int band_launch(const char *domain, BandArgs a)
 		}
 	}
 	else {
-		const int bx = (a.elems + LOGIC_THREADS - 1) / LOGIC_THREADS;
-		dim3 grid(bx, logic_rows_grid(bx, a.height), 1);
+		const int bx = (a.elems + POINTWISE_THREADS - 1) / POINTWISE_THREADS;
+		dim3 grid(bx, pointwise_rows_grid(bx, a.height), 1);
 		Gate gate("logic_band_general");
-		hipLaunchKernelGGL((band_general_kernel<T, OP>), grid, dim3(LOGIC_THREADS, 1, 1), 0, stream(), a);
+		hipLaunchKernelGGL((band_general_kernel<T, OP>), grid, dim3(POINTWISE_THREADS, 1, 1), 0, stream(), a);
 	}
 	VH_CHECK(hipGetLastError());
 	return 0;
@@ -1230,9 +987,9 @@ int band_run(const char *domain, int op, int format, BandArgs a)
 int logic_tile(int what)
 {
 	switch (what) {
-	case 0: return LOGIC_THREADS;
-	case 1: return LOGIC_GROUP;
-	case 2: return LOGIC_GRID_BLOCKS;
+	case 0: return POINTWISE_THREADS;
+	case 1: return POINTWISE_GROUP;
+	case 2: return POINTWISE_GRID_BLOCKS;
 	default: return 0;
 	}
 }

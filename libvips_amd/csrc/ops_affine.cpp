@@ -28,21 +28,6 @@ struct _VipsHipAffinePlan {
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
 struct PlanRef {
 	VipsHipAffinePlan *p;
 	~PlanRef() { vips_hip_affine_plan_free(p); }

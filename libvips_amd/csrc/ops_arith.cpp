@@ -16,30 +16,6 @@ static_assert(ARITH_LAST == VIPS_HIP_ARITH_LAST, "one list of operations");
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
-struct DeviceBlock {
-	void *p;
-	explicit DeviceBlock(size_t size)
-		: p(size ? vips_hip_malloc(size) : nullptr)
-	{
-	}
-	~DeviceBlock() { vips_hip_free(p); }
-};
-
 const char *const NICKNAMES[ARITH_LAST] = { "linear", "invert", "abs", "add", "subtract", "multiply", "divide" };
 
 } // namespace
@@ -97,22 +73,83 @@ int vh::arithmetic_window_pair(const char *domain, const VipsHipRegion *in, cons
 	return 0;
 }
 
+void vh::pointwise_unary_geom(const VipsHipRegion *in, const VipsHipRegion *out, PointwiseGeom *g)
+{
+	memset(g, 0, sizeof(*g));
+	g->in = (const unsigned char *) in->data;
+	g->out = (unsigned char *) out->data;
+	g->in_stride = (long long) in->stride;
+	g->out_stride = (long long) out->stride;
+	g->elems = out->width * out->bands;
+	g->height = out->height;
+	g->bands = out->bands;
+	g->w1 = in->width;
+	g->h1 = in->height;
+	g->b1 = in->bands;
+}
+
+void vh::pointwise_binary_geom(const VipsHipImage *left, const VipsHipImage *right, const VipsHipImage *out, PointwiseGeom *g)
+{
+	memset(g, 0, sizeof(*g));
+	g->in = (const unsigned char *) left->data;
+	g->in2 = (const unsigned char *) right->data;
+	g->out = (unsigned char *) out->data;
+	g->in_stride = (long long) left->stride;
+	g->in2_stride = (long long) right->stride;
+	g->out_stride = (long long) out->stride;
+	g->elems = out->width * out->bands;
+	g->height = out->height;
+	g->bands = out->bands;
+	g->w1 = left->width;
+	g->h1 = left->height;
+	g->b1 = left->bands;
+	g->w2 = right->width;
+	g->h2 = right->height;
+	g->b2 = right->bands;
+}
+
+int vh::binary_operands(const char *domain, VipsHipImage *left, VipsHipImage *right, BinaryPlanFn plan, const void *closure, BinaryOperands *b)
+{
+	if (right->device != left->device) {
+		error(domain, "the images are on different devices");
+		return -1;
+	}
+	if (plan(closure, left, right, b))
+		return -1;
+	// vips__formatalike (arithmetic.c:111-137): vips_cast of what is not in the common format
+	VipsHipImage *im[2] = { left, right };
+	for (int i = 0; i < 2; i++)
+		if (im[i]->format != b->format) {
+			if (vips_hip_cast(im[i], &b->cast[i].im, b->format))
+				return -1;
+			im[i] = b->cast[i].im;
+		}
+	if ((long long) b->width * b->bands >= (1LL << 31)) {
+		error(domain, "image rows too long");
+		return -1;
+	}
+	b->out.im = vips_hip_image_new(b->width, b->height, b->bands, b->out_format, b->interpretation);
+	if (!b->out.im)
+		return -1;
+	pointwise_binary_geom(im[0], im[1], b->out.im, &b->geom);
+	return 0;
+}
+
 namespace {
+
+// the arguments of a call without vectors
+void arith_args(const PointwiseGeom &g, ArithArgs *a)
+{
+	memset(a, 0, sizeof(*a));
+	*static_cast<PointwiseGeom *>(a) = g;
+	a->single = 1;
+}
 
 void unary_args(const VipsHipRegion *in, const VipsHipRegion *out, ArithArgs *a)
 {
-	memset(a, 0, sizeof(*a));
-	a->in = (const unsigned char *) in->data;
-	a->out = (unsigned char *) out->data;
-	a->in_stride = (long long) in->stride;
-	a->out_stride = (long long) out->stride;
-	a->elems = out->width * out->bands;
-	a->height = out->height;
-	a->bands = out->bands;
-	a->w1 = in->width;
-	a->h1 = in->height;
-	a->b1 = in->bands;
-	a->single = 1;
+	PointwiseGeom g;
+	pointwise_unary_geom(in, out, &g);
+	arith_args(g, a);
 }
 
 // invert and abs: the same bands and format on both sides
@@ -162,6 +199,13 @@ int same_image(int op, VipsHipImage *in, VipsHipImage **out)
 	return 0;
 }
 
+int binary_plan(const void *closure, const VipsHipImage *left, const VipsHipImage *right, BinaryOperands *b)
+{
+	return vips_hip_binary_plan(*(const int *) closure, left->width, left->height, left->bands, left->format, left->interpretation,
+		right->width, right->height, right->bands, right->format, right->interpretation, &b->format, &b->out_format, &b->bands,
+		&b->interpretation, &b->width, &b->height);
+}
+
 int binary_image(int op, VipsHipImage *left, VipsHipImage *right, VipsHipImage **out)
 {
 	const char *domain = NICKNAMES[op];
@@ -171,52 +215,14 @@ int binary_image(int op, VipsHipImage *left, VipsHipImage *right, VipsHipImage *
 		error(domain, "null argument");
 		return -1;
 	}
-	if (right->device != left->device) {
-		error(domain, "the images are on different devices");
-		return -1;
-	}
-	int format, out_format, bands, interpretation, width, height;
-	if (vips_hip_binary_plan(op, left->width, left->height, left->bands, left->format, left->interpretation, right->width,
-			right->height, right->bands, right->format, right->interpretation, &format, &out_format, &bands, &interpretation,
-			&width, &height))
-		return -1;
-	// vips__formatalike (arithmetic.c:111-137): vips_cast of what is not in the common format
-	ImageRef cast[2];
-	VipsHipImage *im[2] = { left, right };
-	for (int i = 0; i < 2; i++)
-		if (im[i]->format != format) {
-			if (vips_hip_cast(im[i], &cast[i].im, format))
-				return -1;
-			im[i] = cast[i].im;
-		}
-	if ((long long) width * bands >= (1LL << 31)) {
-		error(domain, "image rows too long");
-		return -1;
-	}
-	ImageRef o(vips_hip_image_new(width, height, bands, out_format, interpretation));
-	if (!o.im)
+	BinaryOperands b;
+	if (binary_operands(domain, left, right, binary_plan, &op, &b))
 		return -1;
 	ArithArgs a;
-	memset(&a, 0, sizeof(a));
-	a.in = (const unsigned char *) im[0]->data;
-	a.in2 = (const unsigned char *) im[1]->data;
-	a.out = (unsigned char *) o.im->data;
-	a.in_stride = (long long) im[0]->stride;
-	a.in2_stride = (long long) im[1]->stride;
-	a.out_stride = (long long) o.im->stride;
-	a.elems = width * bands;
-	a.height = height;
-	a.bands = bands;
-	a.w1 = im[0]->width;
-	a.h1 = im[0]->height;
-	a.b1 = im[0]->bands;
-	a.w2 = im[1]->width;
-	a.h2 = im[1]->height;
-	a.b2 = im[1]->bands;
-	a.single = 1;
-	if (arith_run(domain, op, format, out_format, a))
+	arith_args(b.geom, &a);
+	if (arith_run(domain, op, b.format, b.out_format, a))
 		return -1;
-	*out = o.release();
+	*out = b.out.release();
 	return 0;
 }
 

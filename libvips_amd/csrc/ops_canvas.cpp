@@ -12,21 +12,6 @@ using namespace vh;
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
 // vips_interpretation_max_alpha, iofuncs/header.c:194-206
 double interpretation_max_alpha(int interpretation)
 {

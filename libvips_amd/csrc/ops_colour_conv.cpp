@@ -21,21 +21,6 @@ using namespace vh;
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
 // Operation cache (the role of iofuncs/cache.c for this path): a mask's device tables are
 // built and uploaded once, not per call -- a table upload synchronises the stream, which on a
 // 1024^2 thumbnail costs more than the kernels.  LRU, shared_ptr so an eviction cannot pull

@@ -13,30 +13,6 @@ using namespace vh;
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
-struct DeviceBlock {
-	void *p;
-	explicit DeviceBlock(size_t size)
-		: p(size ? vips_hip_malloc(size) : nullptr)
-	{
-	}
-	~DeviceBlock() { vips_hip_free(p); }
-};
-
 struct ConvRef {
 	VipsHipConv *c;
 	explicit ConvRef(VipsHipConv *conv)

@@ -12,30 +12,6 @@ using namespace vh;
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
-struct DeviceBlock {
-	void *p;
-	explicit DeviceBlock(size_t size)
-		: p(size ? vips_hip_malloc(size) : nullptr)
-	{
-	}
-	~DeviceBlock() { vips_hip_free(p); }
-};
-
 const char *format_name(int format)
 {
 	static const char *names[] = { "uchar", "char", "ushort", "short", "uint", "int", "float", "complex", "double", "dpcomplex" };

@@ -17,21 +17,6 @@ static_assert(BAND_MAX_SOURCES == VIPS_HIP_BANDJOIN_MAX, "one length for bandjoi
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
 // vips_enum_nick of VipsOperationBoolean
 const char *const BOOLEAN_NICKS[BOOLEAN_LAST] = { "and", "or", "eor", "lshift", "rshift" };
 
@@ -158,16 +143,7 @@ int const_gen(const ConstCall &call, const VipsHipRegion *in, const VipsHipRegio
 	}
 	// relational.c:528-529; boolean_const uses c_int whatever the constants were
 	a.is_int = is_int && !format_iscomplex(in->format) && in->format <= VIPS_HIP_FORMAT_INT;
-	a.in = (const unsigned char *) in->data;
-	a.out = (unsigned char *) out->data;
-	a.in_stride = (long long) in->stride;
-	a.out_stride = (long long) out->stride;
-	a.elems = out->width * out->bands;
-	a.height = out->height;
-	a.bands = out->bands;
-	a.w1 = in->width;
-	a.h1 = in->height;
-	a.b1 = in->bands;
+	pointwise_unary_geom(in, out, &a);
 	return logic_run(domain, call.family, call.op, in->format, a);
 }
 
@@ -191,6 +167,17 @@ int const_image(int family, VipsHipImage *in, VipsHipImage **out, int op, const 
 	return whole_image(in, out, bands, vips_hip_logic_format(family, in->format), const_gen_fn, &call);
 }
 
+// closure: the family and the operation, which is checked here: behind the device check, before the plan
+int binary_plan(const void *closure, const VipsHipImage *left, const VipsHipImage *right, BinaryOperands *b)
+{
+	const int family = ((const int *) closure)[0], op = ((const int *) closure)[1];
+	if (check_op(BINARY_NICKNAMES[family], op, family == LOGIC_RELATIONAL ? RELATIONAL_LAST : BOOLEAN_LAST))
+		return -1;
+	return vips_hip_logic_plan(family, left->width, left->height, left->bands, left->format, left->interpretation, right->width,
+		right->height, right->bands, right->format, right->interpretation, &b->format, &b->out_format, &b->bands, &b->interpretation,
+		&b->width, &b->height);
+}
+
 int binary_image(int family, VipsHipImage *left, VipsHipImage *right, VipsHipImage **out, int op)
 {
 	const char *domain = BINARY_NICKNAMES[family];
@@ -200,54 +187,17 @@ int binary_image(int family, VipsHipImage *left, VipsHipImage *right, VipsHipIma
 		error(domain, "null argument");
 		return -1;
 	}
-	if (right->device != left->device) {
-		error(domain, "the images are on different devices");
-		return -1;
-	}
-	if (check_op(domain, op, family == LOGIC_RELATIONAL ? RELATIONAL_LAST : BOOLEAN_LAST))
-		return -1;
-	int format, out_format, bands, interpretation, width, height;
-	if (vips_hip_logic_plan(family, left->width, left->height, left->bands, left->format, left->interpretation, right->width,
-			right->height, right->bands, right->format, right->interpretation, &format, &out_format, &bands, &interpretation,
-			&width, &height))
-		return -1;
-	// vips__formatalike (arithmetic.c:111-137): vips_cast of what is not in the common format
-	ImageRef cast[2];
-	VipsHipImage *im[2] = { left, right };
-	for (int i = 0; i < 2; i++)
-		if (im[i]->format != format) {
-			if (vips_hip_cast(im[i], &cast[i].im, format))
-				return -1;
-			im[i] = cast[i].im;
-		}
-	if ((long long) width * bands >= (1LL << 31)) {
-		error(domain, "image rows too long");
-		return -1;
-	}
-	ImageRef o(vips_hip_image_new(width, height, bands, out_format, interpretation));
-	if (!o.im)
+	const int call[2] = { family, op };
+	BinaryOperands b;
+	if (binary_operands(domain, left, right, binary_plan, call, &b))
 		return -1;
 	LogicArgs a;
 	memset(&a, 0, sizeof(a));
-	a.in = (const unsigned char *) im[0]->data;
-	a.in2 = (const unsigned char *) im[1]->data;
-	a.out = (unsigned char *) o.im->data;
-	a.in_stride = (long long) im[0]->stride;
-	a.in2_stride = (long long) im[1]->stride;
-	a.out_stride = (long long) o.im->stride;
-	a.elems = width * bands;
-	a.height = height;
-	a.bands = bands;
-	a.w1 = im[0]->width;
-	a.h1 = im[0]->height;
-	a.b1 = im[0]->bands;
-	a.w2 = im[1]->width;
-	a.h2 = im[1]->height;
-	a.b2 = im[1]->bands;
+	static_cast<PointwiseGeom &>(a) = b.geom;
 	a.single = 1;
-	if (logic_run(domain, family, op, format, a))
+	if (logic_run(domain, family, op, b.format, a))
 		return -1;
-	*out = o.release();
+	*out = b.out.release();
 	return 0;
 }
 

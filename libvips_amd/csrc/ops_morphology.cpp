@@ -8,34 +8,6 @@
 
 using namespace vh;
 
-namespace {
-
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
-struct DeviceBlock {
-	void *p;
-	explicit DeviceBlock(size_t size)
-		: p(size ? vips_hip_malloc(size) : nullptr)
-	{
-	}
-	~DeviceBlock() { vips_hip_free(p); }
-};
-
-} // namespace
-
 // The checks every neighbourhood gen makes on its pair of regions, and the geometry of the launch: @in must hold the
 // out rect grown by the window (origin win_w / 2, win_h / 2) and clipped to the image.
 int vh::nb_geometry(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out, int win_w, int win_h, NbArgs *a)

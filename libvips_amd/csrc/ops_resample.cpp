@@ -76,21 +76,6 @@ ReducePtr reduce_cached(int kernel, double shrink, int in_size, int out_size, do
 	return r;
 }
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
 VipsHipImage *like(const VipsHipImage *in, int width, int height)
 {
 	return vips_hip_image_new(width, height, in->bands, in->format, in->interpretation);

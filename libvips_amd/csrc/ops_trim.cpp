@@ -15,30 +15,6 @@ static_assert(VIPS_HIP_TRIM_MAX_BACKGROUND == VIPS_HIP_ARITH_MAX_VECTOR, "the ba
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
-struct DeviceBlock {
-	void *p;
-	explicit DeviceBlock(size_t size)
-		: p(size ? vips_hip_malloc(size) : nullptr)
-	{
-	}
-	~DeviceBlock() { vips_hip_free(p); }
-};
-
 int enter(const char *domain, VipsHipImage *in, const void *out1, const void *out2)
 {
 	if (in && bind_to(in)) // run where the pixels live

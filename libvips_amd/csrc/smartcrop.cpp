@@ -19,30 +19,6 @@ int attention_max(const char *domain, const _VipsHipImage *in, unsigned int *res
 
 namespace {
 
-struct ImageRef {
-	VipsHipImage *im;
-	explicit ImageRef(VipsHipImage *i = nullptr)
-		: im(i)
-	{
-	}
-	~ImageRef() { vips_hip_image_unref(im); }
-	VipsHipImage *release()
-	{
-		VipsHipImage *t = im;
-		im = nullptr;
-		return t;
-	}
-};
-
-struct DeviceBlock {
-	void *p;
-	explicit DeviceBlock(size_t size)
-		: p(vips_hip_malloc(size))
-	{
-	}
-	~DeviceBlock() { vips_hip_free(p); }
-};
-
 struct HostBlock {
 	void *p;
 	explicit HostBlock(size_t size)

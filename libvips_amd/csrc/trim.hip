@@ -29,10 +29,7 @@
 //                          the caches and only sends an atomic max for those it improves.  !MEDIAN (line_art) looks
 //                          the centre byte up.
 #include "nbhd_tile.h"
-
-#include <cstdint>
-#include <cstdlib>
-#include <type_traits>
+#include "pointwise.h"
 
 namespace vh {
 
@@ -45,16 +42,6 @@ constexpr int TRIM_GRID_BLOCKS = 1024; // of a launch, four a CU as stats (the g
 constexpr int TRIM_FUSED_TW = 256;    // elements of a fused tile's row
 constexpr int TRIM_FUSED_TH = 8;      // rows of a fused tile
 constexpr int TRIM_FUSED_TILES = 8;   // tiles, one below the other, of a fused block
-
-typedef unsigned char u8;
-typedef signed char s8;
-typedef unsigned short u16;
-typedef short s16;
-typedef unsigned int u32;
-typedef int s32;
-typedef float f32;
-typedef double f64;
-typedef unsigned long long u64;
 
 struct ProjectArgs {
 	const unsigned char *in;
@@ -81,36 +68,6 @@ VH_DEV typename ProjectSum<T>::type project_value(T v)
 		return (S) v;
 	else
 		return (S) (s32) v; // (sign-extended: the int the reference adds)
-}
-
-// element i (a constant once the loops are unrolled) of the four dwords of a group
-template <typename T>
-VH_DEV T trim_take(const unsigned int (&d)[4], int i)
-{
-	if constexpr (sizeof(T) == 1)
-		return (T) (d[i >> 2] >> (8 * (i & 3)));
-	else if constexpr (sizeof(T) == 2)
-		return (T) (d[i >> 1] >> (16 * (i & 1)));
-	else if constexpr (sizeof(T) == 4)
-		return __builtin_bit_cast(T, d[i]);
-	else
-		return __builtin_bit_cast(T, (u64) d[2 * i] | ((u64) d[2 * i + 1] << 32));
-}
-
-template <typename T>
-VH_DEV void trim_put(unsigned int (&w)[4], int i, T v)
-{
-	if constexpr (sizeof(T) == 1)
-		w[i >> 2] |= (unsigned int) (unsigned char) v << (8 * (i & 3));
-	else if constexpr (sizeof(T) == 2)
-		w[i >> 1] |= (unsigned int) (unsigned short) v << (16 * (i & 1));
-	else if constexpr (sizeof(T) == 4)
-		w[i] = __builtin_bit_cast(unsigned int, v);
-	else {
-		const u64 bits = __builtin_bit_cast(u64, v);
-		w[2 * i] = (unsigned int) bits;
-		w[2 * i + 1] = (unsigned int) (bits >> 32);
-	}
 }
 
 // what lane + delta of the wave holds
@@ -234,7 +191,7 @@ project_stream_kernel(ProjectArgs a)
 #pragma unroll
 						for (int j = 0; j < NE; j++)
 							if (j < n)
-								trim_put<T>(d[q], j, ((const T *) row)[e0 + j]);
+								group_put<T>(d[q], j, ((const T *) row)[e0 + j]);
 					}
 				}
 			}
@@ -248,7 +205,7 @@ project_stream_kernel(ProjectArgs a)
 					rel[k] = 0;
 #pragma unroll
 				for (int j = 0; j < NE; j++) {
-					const S v = project_value<T>(trim_take<T>(d[q], j)); // (what lies past the row is zero)
+					const S v = project_value<T>(group_take<T, 4>(d[q], j)); // (what lies past the row is zero)
 					col[j] += v;
 					rel[j % B] += v;
 				}

@@ -263,10 +263,11 @@ def upload_frame(frame):
     return Image.new_from_array(np.ascontiguousarray(frame)[:, :, None])
 
 
-def gen_in_frames(src, out_dtype, out_bands, call, margin):
+def gen_in_frames(src, out_dtype, out_bands, call, margin, odd_stride=False):
     """A generate function with the input and the output as windows of larger frames: `margin` bytes before a row's
     first pel (0 or 4: rows start on dwords; 1 .. 3: they need not), strides that are multiples of 4 (margin 0, 4) or
-    odd.  The output frame's bytes outside the window must stay as they were."""
+    odd.  odd_stride (elements of 1 or 2 bytes): strides one element past a multiple of 4, the margins such that the
+    window's first row still starts on a dword.  The output frame's bytes outside the window must stay as they were."""
     h, w, b = src.shape
     ipel, opel = b * src.dtype.itemsize, out_bands * np.dtype(out_dtype).itemsize
     # rows must start on whole elements: aligned frames keep doubles on 8 bytes, unaligned ones move a row's start by
@@ -276,6 +277,11 @@ def gen_in_frames(src, out_dtype, out_bands, call, margin):
     omargin, ounit = (max(4, oes), max(4, oes)) if margin % 4 == 0 else (margin * oes, oes)
     istride = (imargin + w * ipel + 5 + iunit - 1) // iunit * iunit
     ostride = (omargin + w * opel + 7 + ounit - 1) // ounit * ounit
+    if odd_stride:
+        assert margin % 4 == 0 and ies < 4 and oes < 4
+        istride, ostride = istride + 4 + ies, ostride + 4 + oes
+        # (the window is on row 1 of a frame that starts on a dword)
+        imargin, omargin = 4 + -istride % 4, 4 + -ostride % 4
     fin = np.full((h + 2, istride), 0x3C, np.uint8)
     fin[1:1 + h, imargin:imargin + w * ipel] = src.view(np.uint8).reshape(h, w * ipel)
     fout = np.full((h + 2, ostride), SENTINEL, np.uint8)
@@ -318,6 +324,21 @@ def test_invert_sweep(es, bands, kernel):
             streams = kernel == "stream" or (kernel == "unaligned" and es >= 4)
             assert g.ran == {"arith_stream" if streams else "arith_general": 1}, (g.ran, es, bands, w, h)
             same(got, model_invert(src), (kernel, es, bands, w, h))
+
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
+@pytest.mark.parametrize("bands", [1, 3])
+@pytest.mark.parametrize("es", [1, 2])
+def test_invert_one_row_sweep(es, bands, kernel):
+    """One row is nothing away from a next one, so its stride has no say: a one-row window that starts on a dword
+    streams out of frames whose strides are no multiple of 4; the general kernel gives the same bytes."""
+    dtype = SWEEP_DTYPES[es]
+    for w in sweep_widths(es * bands, es):
+        src = noise(w, 1, dtype, bands, 3000 + w)
+        with general_kernel(kernel == "general"), gated() as g:
+            got = gen_in_frames(src, dtype, bands, lib.vips_hip_invert_gen, 4, odd_stride=True)
+        assert g.ran == {"arith_stream" if kernel == "stream" else "arith_general": 1}, (g.ran, es, bands, w)
+        same(got, model_invert(src), (kernel, es, bands, w))
 
 
 @pytest.mark.parametrize("kernel", ["stream", "general"])

@@ -603,6 +603,31 @@ def test_one_image_sweep(nick, es, bands, kernel):
 
 
 @pytest.mark.parametrize("kernel", ["stream", "general"])
+@pytest.mark.parametrize("bands", [1, 3])
+@pytest.mark.parametrize("es", [1, 2])
+def test_one_row_sweep(es, bands, kernel):
+    """One row is nothing away from a next one, so its stride has no say (the rule this family shares with arithmetic):
+    more_const on a one-row window that starts on a dword, out of frames whose strides are no multiple of 4, and `and`
+    of two one-row images, whose strides are their rows' bytes whatever those are, stream; the general kernel gives
+    the same bytes."""
+    dtype = np.dtype(SWEEP_DTYPES[es])
+    name = "logic_stream" if kernel == "stream" else "logic_general"
+    for w in sweep_widths(es * bands, es):
+        src = noise(w, 1, dtype, bands, 4000 + w)
+        args, call, out_dtype, out_bands = gen_case("relational_const", src)
+        with general_kernel(kernel == "general"), gated() as g:
+            got = gen_in_frames(src, out_dtype, out_bands, call, 4, odd_stride=True)
+        assert g.ran == {name: 1}, (g.ran, es, bands, w)
+        same(got, Ref.run("relational_const", src, args), ("more_const", kernel, es, bands, w))
+        other = noise(w, 1, dtype, bands, 4001 + w)
+        ia, ib = Image.new_from_array(src), Image.new_from_array(other)
+        with general_kernel(kernel == "general"), gated() as g:
+            got = ia.andimage(ib).numpy()
+        assert g.ran == {name: 1} and g.casts == 0, (g.ran, es, bands, w)
+        same(got, model_boolean("and", src, other), ("and", kernel, es, bands, w))
+
+
+@pytest.mark.parametrize("kernel", ["stream", "general"])
 @pytest.mark.parametrize("bands", [1, 2, 3, 4, 5])
 @pytest.mark.parametrize("es", [1, 2, 4, 8])
 def test_several_images_sweep(es, bands, kernel):
