@@ -152,9 +152,14 @@ VIPS_HIP_API int vips_hip_vector_isenabled(void);
  * separately rounded multiplies and adds (convolution/convf.c:163-181).  By default the large
  * float convolutions on integer images (masks 8 or more wide: BASELINE config 5) accumulate
  * with fused multiply-adds instead -- twice the FP64 rate, and the float result differs from the
- * reference's by at most 1 ULP (the tolerance BASELINE.json's north_star grants float paths;
- * measured: a handful of pixels per million).  Enabled (or $VIPS_HIP_EXACT_FLOAT=1 at first use)
- * every float path reproduces the reference bit for bit.  Integer paths are always exact.
+ * reference's by at most 1 ULP where the taps are of one sign and the pels under a window are of
+ * one sign, so that the sum cannot cancel (the tolerance BASELINE.json's north_star grants float
+ * paths; measured: a handful of pixels per million).  A window that holds pels of both signs can
+ * cancel, and what is left of a cancelled sum has no ULP bound in either arithmetic.  Masks
+ * whose non-zero taps differ in sign always take the exact arithmetic, whatever the mode; so do
+ * the operations a decision hangs on (vips_hip_canny, vips_hip_smartcrop's attention search)
+ * while they run.  Enabled (or $VIPS_HIP_EXACT_FLOAT=1 at first use) every float path reproduces
+ * the reference bit for bit.  Integer paths are always exact.
  */
 VIPS_HIP_API void vips_hip_set_exact_float(int enabled);
 VIPS_HIP_API int vips_hip_get_exact_float(void);
@@ -628,6 +633,9 @@ VIPS_HIP_API int vips_hip_compass_gen(const VipsHipCompass *plan, const VipsHipR
  * within a few ulp of a float rounding boundary.  The float kernel COUNTS the pels whose theta would round to another
  * float had atan2's result been 4 ulp off either way: vips_hip_canny_marginal() returns that count for the calling
  * thread's device since it was last read (and clears it).  Zero means bit-identical.
+ * vips_hip_canny's own blur always reproduces the reference's bits, whatever vips_hip_set_exact_float() says: the
+ * gradient and the thinning turn a last bit of the blur into a decision.  vips_hip_canny_gen takes the blur its caller
+ * made.
  * The window must hold the out rect grown by two pels above and to the left and one below and to the right, clipped
  * to the image: rows vips_hip_canny_need() names.  vips_hip_edge_step 3 / 4: the pels / rows a block makes.
  */

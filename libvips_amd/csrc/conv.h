@@ -22,6 +22,9 @@ struct _VipsHipConv {
 	void *d_dense; // int / double [mask_width * mask_height], zeros kept (tiled kernels)
 	double *d_dense8; // convf: rows zero-padded to np8 doubles (grouped kernel)
 	int np8;
+	// convf: the non-zero taps are all of one sign, so a sum over pels of one sign cannot cancel -- the only masks the
+	// default float mode's fused multiply-adds take (conv_one_sign, conv.hip); the others always get exact arithmetic
+	bool one_sign;
 	// the Highway variant of convi on uchar (convi.c:925-1120): 8-bit mantissas sharing one
 	// exponent; hwy_ok is false when vips_convi_intize refuses the mask (the C path then runs)
 	bool hwy_ok;

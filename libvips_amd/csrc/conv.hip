@@ -606,15 +606,28 @@ convf_rows_lds(ConvArgs a)
 	}
 }
 
+// The default float mode's rule for a convf mask (the same as convsep_stream.hip's): fused multiply-adds only where
+// the non-zero taps are all of one sign.  Taps that differ in sign can cancel, and a cancelling sum has no 1 ULP
+// bound -- on a flat image a difference of Gaussians leaves nothing but the roundings -- so such a mask takes the
+// FUSED = false kernels whatever the mode.  (BASELINE config 5's Gaussian is all positive: fused.)
+static bool conv_one_sign(const std::vector<double> &coefff)
+{
+	for (const double v : coefff)
+		if ((v < 0.0) != (coefff[0] < 0.0))
+			return false;
+	return true;
+}
+
+// fuse: FUSED = true (the default float mode on a mask conv_one_sign passes)
 template <typename TIN>
-static int launch_convf_rows_lds(const ConvArgs &a, const char *name)
+static int launch_convf_rows_lds(const ConvArgs &a, const char *name, bool fuse)
 {
 	constexpr int R = 4;
 	dim3 grid((a.out_width + CONVF_LDS_SPAN - 1) / CONVF_LDS_SPAN, (a.out_height + R - 1) / R, 1);
 	if (grid.y > 65535)
 		return 1;
 	Gate gate(name);
-	if (vips_hip_get_exact_float())
+	if (!fuse)
 		hipLaunchKernelGGL((convf_rows_lds<TIN, R, false>), grid, dim3(256, 1, 1), 0, stream(), a);
 	else
 		hipLaunchKernelGGL((convf_rows_lds<TIN, R, true>), grid, dim3(256, 1, 1), 0, stream(), a);
@@ -624,14 +637,15 @@ static int launch_convf_rows_lds(const ConvArgs &a, const char *name)
 
 // The tiled kernel wins whenever a thread's TILE outputs share taps; masks that are a
 // single element (or tiny images) keep the general kernel.
+// fuse (convf only): take the FUSED = true instantiations.
 template <typename TIN, typename TOUT, int MODE>
-static int launch_conv_best(const ConvArgs &a, const char *name)
+static int launch_conv_best(const ConvArgs &a, const char *name, bool fuse = false)
 {
 	if constexpr (MODE == 2 && std::is_integral<TIN>::value && sizeof(TIN) <= 2 && std::is_same<TOUT, float>::value) {
 		// one band, masks 8..64 wide, images wide enough to fill blocks: the LDS row-streaming kernel
 		if (a.epp == 1 && a.mask_width >= 8 && a.mask_width <= CONVF_LDS_MAXW && a.mask_height >= 4 &&
 			a.out_width >= 512 && a.dense8 && !getenv("VIPS_HIP_NO_GROUPED_CONV") && !getenv("VIPS_HIP_NO_LDS_CONV")) {
-			const int r = launch_convf_rows_lds<TIN>(a, name);
+			const int r = launch_convf_rows_lds<TIN>(a, name, fuse);
 			if (r <= 0)
 				return r;
 		}
@@ -643,7 +657,7 @@ static int launch_conv_best(const ConvArgs &a, const char *name)
 			Gate gate(name);
 #define GROUPED(EPP, FUSED) \
 	hipLaunchKernelGGL((convf_grouped<TIN, TOUT, EPP, FUSED>), grid, dim3(256, 1, 1), 0, stream(), a)
-			if (vips_hip_get_exact_float()) {
+			if (!fuse) {
 				switch (a.epp) {
 				case 1: GROUPED(1, false); break;
 				case 3: GROUPED(3, false); break;
@@ -827,6 +841,7 @@ VipsHipConv *vips_hip_conv_new(const double *mask, int mask_width, int mask_heig
 	c->d_dense = nullptr;
 	c->d_dense8 = nullptr;
 	c->np8 = 0;
+	c->one_sign = false;
 	c->hwy_ok = c->no_vector = false;
 	c->hwy_exp = 0;
 	c->d_hwy_coeff = c->d_hwy_dense = nullptr;
@@ -873,6 +888,7 @@ VipsHipConv *vips_hip_conv_new(const double *mask, int mask_width, int mask_heig
 			c->pos.push_back(0);
 		}
 		c->nnz = (int) c->coefff.size();
+		c->one_sign = conv_one_sign(c->coefff);
 	}
 	return c;
 }
@@ -1046,15 +1062,17 @@ int vips_hip_conv_gen(const VipsHipConv *conv, const VipsHipRegion *in, const Vi
 		}
 	}
 	else {
+		// fused multiply-adds: the default float mode, on masks whose sums cannot cancel (conv_one_sign)
+		const bool fuse = !vips_hip_get_exact_float() && c->one_sign;
 		switch (fmt) {
-		case VIPS_HIP_FORMAT_UCHAR: return launch_conv_best<unsigned char, float, 2>(a, "convf");
-		case VIPS_HIP_FORMAT_CHAR: return launch_conv_best<signed char, float, 2>(a, "convf");
-		case VIPS_HIP_FORMAT_USHORT: return launch_conv_best<unsigned short, float, 2>(a, "convf");
-		case VIPS_HIP_FORMAT_SHORT: return launch_conv_best<short, float, 2>(a, "convf");
-		case VIPS_HIP_FORMAT_UINT: return launch_conv_best<unsigned int, float, 2>(a, "convf");
-		case VIPS_HIP_FORMAT_INT: return launch_conv_best<int, float, 2>(a, "convf");
-		case VIPS_HIP_FORMAT_FLOAT: return launch_conv_best<float, float, 2>(a, "convf");
-		case VIPS_HIP_FORMAT_DOUBLE: return launch_conv_best<double, double, 2>(a, "convf");
+		case VIPS_HIP_FORMAT_UCHAR: return launch_conv_best<unsigned char, float, 2>(a, "convf", fuse);
+		case VIPS_HIP_FORMAT_CHAR: return launch_conv_best<signed char, float, 2>(a, "convf", fuse);
+		case VIPS_HIP_FORMAT_USHORT: return launch_conv_best<unsigned short, float, 2>(a, "convf", fuse);
+		case VIPS_HIP_FORMAT_SHORT: return launch_conv_best<short, float, 2>(a, "convf", fuse);
+		case VIPS_HIP_FORMAT_UINT: return launch_conv_best<unsigned int, float, 2>(a, "convf", fuse);
+		case VIPS_HIP_FORMAT_INT: return launch_conv_best<int, float, 2>(a, "convf", fuse);
+		case VIPS_HIP_FORMAT_FLOAT: return launch_conv_best<float, float, 2>(a, "convf", fuse);
+		case VIPS_HIP_FORMAT_DOUBLE: return launch_conv_best<double, double, 2>(a, "convf", fuse);
 		default: break;
 		}
 	}

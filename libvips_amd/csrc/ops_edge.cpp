@@ -583,6 +583,9 @@ long long vips_hip_canny_marginal(void)
 int vips_hip_canny(VipsHipImage *in, VipsHipImage **out, double sigma, int precision)
 {
 	const char *domain = "canny";
+	// decisions hang on the floats (the gradient is a difference of neighbours, thinning keeps or zeroes a pel): the
+	// blur reproduces the reference's bits while this runs, whatever the process-wide float mode is
+	ScopedExactFloat exact;
 	if (in && bind_to(in)) // run where the pixels live
 		return -1;
 	if (!in || !out) {
