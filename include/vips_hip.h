@@ -1035,6 +1035,57 @@ VIPS_HIP_API int vips_hip_similarity(VipsHipImage *in, VipsHipImage **out, doubl
 	const VipsHipAffine *args);
 VIPS_HIP_API int vips_hip_rotate(VipsHipImage *in, VipsHipImage **out, double angle, const VipsHipAffine *args);
 
+/* ------------------------------------------------ mapim and xyz
+ *
+ * vips_mapim (resample/mapim.c): output pel (x, y) is the input resampled at the coordinate that pel (x, y) of @index
+ * holds.  The index has two bands of any non-complex format, or one complex band (real part x); the result has the
+ * index's size and the input's bands, format and interpretation.  Images are what vips_affine takes here: uchar ... int
+ * and float, pels of up to VIPS_HIP_AFFINE_MAX_PEL bytes, the nearest / bilinear / bicubic interpolators, every
+ * `extend`; double and complex images and every other interpolator are refused by name, and so is a complex index of
+ * more than one band (the reference takes it and reads every second pel of it).
+ * An index component is turned into a coordinate in the arithmetic of its own type (mapim.c:228-305): integers as
+ * integers, float and complex in float -- (x + window_offset) + 1, each sum rounded to float --, double in double.
+ * A pel whose index holds a NaN, lies below -1 or at or beyond size + 1 is the background ink.
+ */
+typedef struct {
+	int interpolate; /* VipsHipInterpolate; any other value is refused */
+	int extend;      /* VipsHipExtend */
+	int premultiplied;
+	int n_background; /* 1 or the band count */
+	double background[VIPS_HIP_AFFINE_MAX_BACKGROUND];
+} VipsHipMapim;
+/* bilinear, extend background, background 0, not premultiplied */
+VIPS_HIP_API void vips_hip_mapim_defaults(VipsHipMapim *args);
+/* Whole images, the premultiply / unpremultiply / cast chain of mapim.c:482-531 included: an image with alpha (by its
+ * interpretation and bands) and premultiplied == 0 is resampled as the float image vips_premultiply makes of it. */
+VIPS_HIP_API int vips_hip_mapim(VipsHipImage *in, VipsHipImage *index, VipsHipImage **out, const VipsHipMapim *args);
+/* vips_mapim_region_minmax and the need of vips_mapim_gen (mapim.c:145-224, :351-365) for a rect of the index, an image
+ * in device memory: one read-only launch and 16 bytes back.  need[] is the rect of the input image (in_width x
+ * in_height) that the rect reads, clipped to it, as vips_hip_affine_need reports it; need[2] or need[3] is 0 when
+ * every pel of the rect is ink.  Components that are NaN are skipped.  (The reference starts its scan from the rect's
+ * FIRST pel whatever it holds: for a rect that starts with a NaN its answer is its machine's, and differs from this
+ * one.  The pixels do not depend on it.) */
+VIPS_HIP_API int vips_hip_mapim_need(const VipsHipRegion *index_region, const VipsHipMapim *args, int in_width, int in_height,
+	int need[4]);
+/* The host half of the above: bounds[] = min x, min y, max x, max y of the index's components as doubles; floor /
+ * ceil, the clip to [-1, VIPS_MAX_COORD], the stencil, the offset of 1, the intersection with the embedded image. */
+VIPS_HIP_API int vips_hip_mapim_bounds_need(const double bounds[4], const VipsHipMapim *args, int in_width, int in_height,
+	int need[4]);
+/* vips_mapim_gen (mapim.c:307-428) on regions, which may be strided windows of larger frames: @out_region and
+ * @index_region are the same rect of the output and of the index, @in_region a window of the in_width x in_height
+ * input that must cover vips_hip_mapim_need() of the rect ("input region too small" otherwise: the bounds pass runs to
+ * check, unless the window is the whole image; an all-ink rect accepts any window).  The regions' image is resampled
+ * as it is -- no premultiply chain -- and extend white paints 255. */
+VIPS_HIP_API int vips_hip_mapim_gen(const VipsHipRegion *in_region, const VipsHipRegion *index_region,
+	const VipsHipRegion *out_region, const VipsHipMapim *args, int in_width, int in_height);
+/* The kernels' units, for tests that want sizes round them: 0 / 1 the pels / rows of a block's patch of the output,
+ * 2 / 3 of a wave's patch, 4 the most blocks a bounds launch has, 5 the threads of a block of the bounds and xyz
+ * kernels, 6 the bytes of a group of the xyz kernel; -1 for anything else. */
+VIPS_HIP_API int vips_hip_mapim_step(int what);
+/* vips_xyz (create/xyz.c) in two dimensions: a two-band uint image of interpretation multiband whose pel (x, y) holds
+ * (x, y), made on the device. */
+VIPS_HIP_API int vips_hip_xyz(VipsHipImage **out, int width, int height);
+
 /* ------------------------------------------------ canvas and alpha: embed / gravity / insert / join, flatten, addalpha
  *
  * vips_embed and vips_gravity (conversion/embed.c), vips_insert (insert.c) and vips_join (join.c): exact copies of

@@ -87,6 +87,19 @@ class Affine(ctypes.Structure):
     ]
 
 
+class Mapim(ctypes.Structure):
+    """VipsHipMapim (include/vips_hip.h): the optional arguments of vips_mapim."""
+
+    MAX_BACKGROUND = 64
+    _fields_ = [
+        ("interpolate", ctypes.c_int),
+        ("extend", ctypes.c_int),
+        ("premultiplied", ctypes.c_int),
+        ("n_background", ctypes.c_int),
+        ("background", ctypes.c_double * 64),
+    ]
+
+
 class Embed(ctypes.Structure):
     """VipsHipEmbed (include/vips_hip.h): the optional arguments of vips_embed / vips_gravity."""
 
@@ -394,6 +407,14 @@ _SIGNATURES = {
     "vips_hip_affine": (c_int, [c_void_p, P(c_void_p), P(Affine)]),
     "vips_hip_similarity": (c_int, [c_void_p, P(c_void_p), c_double, c_double, P(Affine)]),
     "vips_hip_rotate": (c_int, [c_void_p, P(c_void_p), c_double, P(Affine)]),
+    # mapim, xyz
+    "vips_hip_mapim_defaults": (None, [P(Mapim)]),
+    "vips_hip_mapim": (c_int, [c_void_p, c_void_p, P(c_void_p), P(Mapim)]),
+    "vips_hip_mapim_need": (c_int, [RegionP, P(Mapim), c_int, c_int, P(c_int)]),
+    "vips_hip_mapim_bounds_need": (c_int, [P(c_double), P(Mapim), c_int, c_int, P(c_int)]),
+    "vips_hip_mapim_gen": (c_int, [RegionP, RegionP, RegionP, P(Mapim), c_int, c_int]),
+    "vips_hip_mapim_step": (c_int, [c_int]),
+    "vips_hip_xyz": (c_int, [P(c_void_p), c_int, c_int]),
     # embed / gravity / insert / join, flatten, addalpha
     "vips_hip_embed_defaults": (None, [P(Embed)]),
     "vips_hip_flatten_defaults": (None, [P(Flatten)]),

@@ -24,49 +24,9 @@ namespace vh {
 
 constexpr int AFFINE_BW = 16, AFFINE_BH = 16; // a block's patch of the output: waves of 16 x 4
 
+// (the fetch through the six extend modes: EmbedFetch, interp_device.h, shared with mapim.hip)
 template <typename T>
-struct AffineFetch {
-	const AffineArgs &a;
-	// embedded (ex, ey) -> the pel of the embed: the original pixel (px, py) sits at (px + off, py + off)
-	__device__ __forceinline__ T operator()(int ex, int ey, int z) const
-	{
-		const int off = a.window_offset + 1;
-		int px = ex - off, py = ey - off;
-		const bool outside = (unsigned int) px >= (unsigned int) a.im_width || (unsigned int) py >= (unsigned int) a.im_height;
-		if (outside) {
-			switch (a.extend) {
-			case VIPS_HIP_EXTEND_COPY:
-				break; // (the clamp below)
-			case VIPS_HIP_EXTEND_REPEAT:
-				// embed.c:378-396: clock arithmetic
-				px %= a.im_width;
-				py %= a.im_height;
-				px += px < 0 ? a.im_width : 0;
-				py += py < 0 ? a.im_height : 0;
-				break;
-			case VIPS_HIP_EXTEND_MIRROR: {
-				// embed.c:398-431: tiles of the image and its reflection, period twice the size
-				const int w2 = 2 * a.im_width, h2 = 2 * a.im_height;
-				px %= w2;
-				py %= h2;
-				px += px < 0 ? w2 : 0;
-				py += py < 0 ? h2 : 0;
-				px = px < a.im_width ? px : w2 - 1 - px;
-				py = py < a.im_height ? py : h2 - 1 - py;
-				break;
-			}
-			default:
-				return ((const T *) a.fill)[z];
-			}
-		}
-		px = min(max(px, 0), a.im_width - 1);
-		py = min(max(py, 0), a.im_height - 1);
-		// never outside the window (the host has checked that the window holds what the rect needs)
-		px = min(max(px - a.in_left, 0), a.in_width - 1);
-		py = min(max(py - a.in_top, 0), a.in_height - 1);
-		return ((const T *) (a.in + (long long) py * a.in_stride))[(long long) px * a.bands + z];
-	}
-};
+using AffineFetch = EmbedFetch<T, AffineArgs>;
 
 template <typename T, int INTERP>
 __global__ void __launch_bounds__(AFFINE_BW * AFFINE_BH)

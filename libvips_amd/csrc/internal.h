@@ -300,6 +300,57 @@ struct AffineArgs {
 };
 // format: uchar .. int or float; interpolate: VipsHipInterpolate
 int affine_run(const char *domain, AffineArgs a, int format, int interpolate);
+// ops_affine.cpp: what vips_affine and vips_mapim share on the host.  resample_check: the interpolator, the extend and
+// the image format are ones the path takes (refused by name otherwise).  resample_pels: the ink and the embed's fill
+// pel of vips__vector_to_ink and embed.c:270-298, the premultiply chain's decision and the stencil
+// (interpolate.c:150-167); resample_fill_premultiply: the chain's fill pel through vips_premultiply, once.
+struct ResamplePels {
+	bool chain;  // premultiply -> resample -> unpremultiply -> cast
+	int kformat; // the format of the image the kernel resamples
+	int window_size, window_offset;
+	bool fill_ready;
+	unsigned char ink[VIPS_HIP_AFFINE_MAX_PEL];
+	unsigned char fill[VIPS_HIP_AFFINE_MAX_PEL]; // in the image's own format until resample_fill_premultiply
+};
+int resample_check(const char *domain, int interpolate, int extend, int format);
+int resample_pels(const char *domain, int interpolate, int extend, int premultiplied, int n_background, const double *background,
+	int bands, int format, int interpretation, ResamplePels *p);
+int resample_fill_premultiply(const char *domain, ResamplePels *p, int bands, int format, int interpretation);
+// ... one axis of the embedded rect [e0, e1] as pels of the image: what EmbedFetch (interp_device.h) reads for it
+void embedded_axis_to_image(int extend, int off, int size, int e0, int e1, int *p0, int *p1);
+// mapim.hip: vips_mapim_gen on checked regions (ops_mapim.cpp checks them and fills everything): output pel (i, y) of
+// the rect reads index pel (i, y) -- two elements of index_format, or one complex element -- and gathers the input at
+// it through EmbedFetch.  The fields the fetch reads are AffineArgs'.
+struct MapimArgs {
+	const unsigned char *in;
+	const unsigned char *index;
+	unsigned char *out;
+	long long in_stride, index_stride, out_stride; // bytes
+	int in_left, in_top, in_width, in_height;      // the input window, pels of the whole image; in_width == 0: no window
+	int im_width, im_height;                       // the whole input image
+	int out_width, out_height;                     // the rect: `index` and `out` point at its first pel
+	int bands;                                     // elements a pel of the input
+	int index_format;
+	int index_wide; // every index pel lies on a multiple of its own size: one load a pel
+	int window_offset;
+	int extend;         // VipsHipExtend
+	const void *tables; // BicubicTables, interp_device.h
+	unsigned char ink[VIPS_HIP_AFFINE_MAX_PEL];  // the pel of what the coordinate stage rejects
+	unsigned char fill[VIPS_HIP_AFFINE_MAX_PEL]; // the pel round the image under extend black / white / background
+};
+int mapim_run(const char *domain, MapimArgs a, int format, int interpolate);
+// ... vips_mapim_region_minmax of a rect of the index in one launch: bounds[0 .. 3] = min x, min y, max x, max y over
+// the pels without a NaN, after floor / ceil and the clip to [-1, VIPS_MAX_COORD] (both monotonic: the extremes are
+// taken in the index's own type, block by block, and merged as integers).  bounds is device memory the kernel's host
+// side initialises; a rect of nothing but NaN leaves min > max.
+constexpr int MAPIM_MAX_COORD = 10000000; // VIPS_MAX_COORD's default
+int mapim_bounds_run(const char *domain, const unsigned char *index, long long index_stride, int width, int height, int index_format,
+	int *bounds);
+// ... vips_xyz: pel (x, y) of a two-band uint image holds (x, y)
+int xyz_run(const char *domain, unsigned char *out, long long out_stride, int width, int height);
+// mapim_tile: 0 / 1 the pels / rows of a block's patch, 2 / 3 of a wave's, 4 the most blocks a bounds launch has,
+// 5 the threads of a block of the bounds and xyz kernels, 6 the bytes of a group of the xyz kernel
+int mapim_tile(int what);
 // canvas.hip: vips_embed, vips_gravity, vips_insert and vips_join on checked geometry (ops_canvas.cpp checks everything):
 // ONE launch writes the rect (out_left, out_top, out_width, out_height) of a canvas.  Canvas pel (X, Y) is the sub-image's
 // pel where the sub-image lies, else the main image's pel where that lies, else -- by `mode` -- the ink, or the main

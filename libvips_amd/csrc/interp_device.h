@@ -88,6 +88,53 @@ static __device__ __forceinline__ double dot4(double c0, double v0, double c1, d
 	return s;
 }
 
+// The fetch of affine.hip and mapim.hip: the vips_embed both operations put in front of themselves (conversion/embed.c),
+// never materialised.  Embedded (ex, ey) becomes a source pel or the fill pel: the original pixel (px, py) sits at
+// (px + off, py + off), off = window_offset + 1.  A is the kernel's argument struct (AffineArgs, MapimArgs: the fields
+// in, in_stride, in_left .. in_height, im_width, im_height, bands, window_offset, extend, fill).
+template <typename T, typename A>
+struct EmbedFetch {
+	const A &a;
+	__device__ __forceinline__ T operator()(int ex, int ey, int z) const
+	{
+		const int off = a.window_offset + 1;
+		int px = ex - off, py = ey - off;
+		const bool outside = (unsigned int) px >= (unsigned int) a.im_width || (unsigned int) py >= (unsigned int) a.im_height;
+		if (outside) {
+			switch (a.extend) {
+			case VIPS_HIP_EXTEND_COPY:
+				break; // (the clamp below)
+			case VIPS_HIP_EXTEND_REPEAT:
+				// embed.c:378-396: clock arithmetic
+				px %= a.im_width;
+				py %= a.im_height;
+				px += px < 0 ? a.im_width : 0;
+				py += py < 0 ? a.im_height : 0;
+				break;
+			case VIPS_HIP_EXTEND_MIRROR: {
+				// embed.c:398-431: tiles of the image and its reflection, period twice the size
+				const int w2 = 2 * a.im_width, h2 = 2 * a.im_height;
+				px %= w2;
+				py %= h2;
+				px += px < 0 ? w2 : 0;
+				py += py < 0 ? h2 : 0;
+				px = px < a.im_width ? px : w2 - 1 - px;
+				py = py < a.im_height ? py : h2 - 1 - py;
+				break;
+			}
+			default:
+				return ((const T *) a.fill)[z];
+			}
+		}
+		px = min(max(px, 0), a.im_width - 1);
+		py = min(max(py, 0), a.im_height - 1);
+		// never outside the window (the host has checked that the window holds what the rect needs)
+		px = min(max(px - a.in_left, 0), a.in_width - 1);
+		py = min(max(py - a.in_top, 0), a.in_height - 1);
+		return ((const T *) (a.in + (long long) py * a.in_stride))[(long long) px * a.bands + z];
+	}
+};
+
 // One pel of `bands` elements at q from the embedded coordinate (x, y); INTERP 0 nearest, 1 bilinear, 2 bicubic.
 template <typename T, int INTERP, typename F>
 static __device__ __forceinline__ void interp_pel(T *q, const double x, const double y, const int bands,

@@ -125,11 +125,11 @@ void element_to_format(double real, int format, unsigned char *dst)
 	}
 }
 
-void vector_to_ink(const VipsHipAffine *args, int bands, int format, unsigned char *dst)
+void vector_to_ink(const double *background, int n_background, int bands, int format, unsigned char *dst)
 {
 	const int es = format_sizeof(format);
 	for (int z = 0; z < bands; z++)
-		element_to_format(args->background[args->n_background == bands ? z : 0], format, dst + (size_t) z * es);
+		element_to_format(background[n_background == bands ? z : 0], format, dst + (size_t) z * es);
 }
 
 struct Rect {
@@ -181,8 +181,12 @@ Rect need_embedded(const VipsHipAffinePlan *p, int left, int top, int width, int
 	return Rect{(int) x0, (int) y0, (int) (x1 - x0), (int) (y1 - y0)};
 }
 
-// one axis of the embedded rect [e0, e1] as pels of the image: what the fetch of affine.hip reads for it
-void axis_to_image(int extend, int off, int size, int e0, int e1, int *p0, int *p1)
+} // namespace
+
+namespace vh {
+
+// one axis of the embedded rect [e0, e1] as pels of the image: what the fetch of affine.hip and mapim.hip reads for it
+void embedded_axis_to_image(int extend, int off, int size, int e0, int e1, int *p0, int *p1)
 {
 	const bool border = e0 < off || e1 >= off + size;
 	if (border && (extend == VIPS_HIP_EXTEND_REPEAT || extend == VIPS_HIP_EXTEND_MIRROR)) {
@@ -195,7 +199,100 @@ void axis_to_image(int extend, int off, int size, int e0, int e1, int *p0, int *
 	*p1 = b < 0 ? 0 : (b > size - 1 ? size - 1 : b);
 }
 
-} // namespace
+int resample_check(const char *domain, int interpolate, int extend, int format)
+{
+	if (interpolate < VIPS_HIP_INTERPOLATE_NEAREST || interpolate > VIPS_HIP_INTERPOLATE_BICUBIC) {
+		error(domain, "interpolator %d is outside the HIP path (nearest, bilinear, bicubic)", interpolate);
+		return -1;
+	}
+	if (extend < VIPS_HIP_EXTEND_BLACK || extend > VIPS_HIP_EXTEND_BACKGROUND) {
+		error(domain, "enum 'VipsExtend' has no member %d", extend);
+		return -1;
+	}
+	if (format_iscomplex(format)) {
+		error(domain, "complex images are outside the HIP path");
+		return -1;
+	}
+	if (format == VIPS_HIP_FORMAT_DOUBLE) {
+		error(domain, "double images are outside the HIP path");
+		return -1;
+	}
+	if (format_sizeof(format) == 0) {
+		error(domain, "unknown band format %d", format);
+		return -1;
+	}
+	return 0;
+}
+
+int resample_pels(const char *domain, int interpolate, int extend, int premultiplied, int n_background, const double *background,
+	int bands, int format, int interpretation, ResamplePels *p)
+{
+	p->window_size = interpolate == VIPS_HIP_INTERPOLATE_NEAREST ? 1 : interpolate == VIPS_HIP_INTERPOLATE_BILINEAR ? 2 : 4;
+	p->window_offset = p->window_size / 2 - 1 > 0 ? p->window_size / 2 - 1 : 0; // interpolate.c:150-167
+	p->chain = false;
+	p->kformat = format;
+	p->fill_ready = true;
+	memset(p->ink, 0, sizeof(p->ink));
+	memset(p->fill, 0, sizeof(p->fill));
+	// vips__vector_to_ink -> vips_linear -> vips_check_vector, iofuncs/error.c:1118-1140
+	if (n_background < 1 || n_background > VIPS_HIP_AFFINE_MAX_BACKGROUND || !(n_background == bands || n_background == 1 || bands == 1)) {
+		if (bands == 1)
+			error("linear", "vector must have 1 element");
+		else
+			error("linear", "vector must have 1 or %d elements", bands);
+		return -1;
+	}
+	const int ibands = interpretation_bands(interpretation);
+	p->chain = ibands > 0 && bands > ibands && !premultiplied;
+	if (p->chain)
+		p->kformat = VIPS_HIP_FORMAT_FLOAT;
+	if ((long long) bands * format_sizeof(p->kformat) > VIPS_HIP_AFFINE_MAX_PEL) {
+		error(domain, "pels of more than %d bytes are outside the HIP path", VIPS_HIP_AFFINE_MAX_PEL);
+		return -1;
+	}
+	// the pel the embed paints round the image (embed.c:270-298), in the image's own format
+	const size_t pel = (size_t) bands * format_sizeof(format);
+	if (extend == VIPS_HIP_EXTEND_WHITE) {
+		// vips_region_paint (iofuncs/region.c:909-956): memset for the integer formats, the value for float
+		const int white = (int) interpretation_max_alpha(interpretation);
+		if (format == VIPS_HIP_FORMAT_FLOAT) {
+			const float v = (float) white;
+			for (int z = 0; z < bands; z++)
+				memcpy(p->fill + (size_t) z * sizeof(float), &v, sizeof(float));
+		}
+		else
+			memset(p->fill, white, pel);
+	}
+	else if (extend == VIPS_HIP_EXTEND_BACKGROUND)
+		vector_to_ink(background, n_background, bands, format, p->fill);
+	p->fill_ready = !p->chain;
+	// the ink of what the clip rejects, in the format of the resampled image and not premultiplied (affine.c:565-571)
+	vector_to_ink(background, n_background, bands, p->kformat, p->ink);
+	return 0;
+}
+
+// the fill pel of the premultiplied image: the image's own pel through vips_premultiply (the embed comes first,
+// affine.c:530-563, mapim.c:472-498)
+int resample_fill_premultiply(const char *domain, ResamplePels *p, int bands, int format, int interpretation)
+{
+	if (p->fill_ready)
+		return 0;
+	ImageRef one(vips_hip_image_new_from_memory(p->fill, 1, 1, bands, format, interpretation));
+	ImageRef pre;
+	if (!one.im || vips_hip_premultiply(one.im, &pre.im, 0))
+		return -1;
+	if (pre.im->format != VIPS_HIP_FORMAT_FLOAT) {
+		error(domain, "premultiply did not make a float image");
+		return -1;
+	}
+	memset(p->fill, 0, sizeof(p->fill));
+	if (vips_hip_image_write_to_memory(pre.im, p->fill))
+		return -1;
+	p->fill_ready = true;
+	return 0;
+}
+
+} // namespace vh
 
 extern "C" {
 
@@ -219,26 +316,8 @@ VipsHipAffinePlan *vips_hip_affine_plan_new(const VipsHipAffine *args, int width
 		error(domain, "bad arguments");
 		return nullptr;
 	}
-	if (args->interpolate < VIPS_HIP_INTERPOLATE_NEAREST || args->interpolate > VIPS_HIP_INTERPOLATE_BICUBIC) {
-		error(domain, "interpolator %d is outside the HIP path (nearest, bilinear, bicubic)", args->interpolate);
+	if (resample_check(domain, args->interpolate, args->extend, format))
 		return nullptr;
-	}
-	if (args->extend < VIPS_HIP_EXTEND_BLACK || args->extend > VIPS_HIP_EXTEND_BACKGROUND) {
-		error(domain, "enum 'VipsExtend' has no member %d", args->extend);
-		return nullptr;
-	}
-	if (format_iscomplex(format)) {
-		error(domain, "complex images are outside the HIP path");
-		return nullptr;
-	}
-	if (format == VIPS_HIP_FORMAT_DOUBLE) {
-		error(domain, "double images are outside the HIP path");
-		return nullptr;
-	}
-	if (format_sizeof(format) == 0) {
-		error(domain, "unknown band format %d", format);
-		return nullptr;
-	}
 	// vips__transform_calc_inverse, transform.c:52-72
 	const double det = args->a * args->d - args->b * args->c;
 	if (fabs(det) < 2.0 * DBL_MIN) {
@@ -294,41 +373,16 @@ VipsHipAffinePlan *vips_hip_affine_plan_new(const VipsHipAffine *args, int width
 		error("VipsImage", "bad dimensions");
 		return nullptr;
 	}
-	// vips__vector_to_ink -> vips_linear -> vips_check_vector, iofuncs/error.c:1118-1140
-	if (args->n_background < 1 || args->n_background > VIPS_HIP_AFFINE_MAX_BACKGROUND ||
-		!(args->n_background == bands || args->n_background == 1 || bands == 1)) {
-		if (bands == 1)
-			error("linear", "vector must have 1 element");
-		else
-			error("linear", "vector must have 1 or %d elements", bands);
+	// the ink, the embed's fill pel and the premultiply chain
+	ResamplePels pels;
+	if (resample_pels(domain, args->interpolate, args->extend, args->premultiplied, args->n_background, args->background, bands, format,
+			interpretation, &pels))
 		return nullptr;
-	}
-	const int ibands = interpretation_bands(interpretation);
-	p->chain = ibands > 0 && bands > ibands && !args->premultiplied;
-	if (p->chain)
-		p->kformat = VIPS_HIP_FORMAT_FLOAT;
-	if ((long long) bands * format_sizeof(p->kformat) > VIPS_HIP_AFFINE_MAX_PEL) {
-		error(domain, "pels of more than %d bytes are outside the HIP path", VIPS_HIP_AFFINE_MAX_PEL);
-		return nullptr;
-	}
-	// the pel the embed paints round the image (embed.c:270-298), in the image's own format
-	const size_t pel = (size_t) bands * format_sizeof(format);
-	if (args->extend == VIPS_HIP_EXTEND_WHITE) {
-		// vips_region_paint (iofuncs/region.c:909-956): memset for the integer formats, the value for float
-		const int white = (int) interpretation_max_alpha(interpretation);
-		if (format == VIPS_HIP_FORMAT_FLOAT) {
-			const float v = (float) white;
-			for (int z = 0; z < bands; z++)
-				memcpy(p->fill + (size_t) z * sizeof(float), &v, sizeof(float));
-		}
-		else
-			memset(p->fill, white, pel);
-	}
-	else if (args->extend == VIPS_HIP_EXTEND_BACKGROUND)
-		vector_to_ink(args, bands, format, p->fill);
-	p->fill_ready = !p->chain;
-	// the ink of what the clip rejects, in the format of the resampled image and not premultiplied (affine.c:565-571)
-	vector_to_ink(args, bands, p->kformat, p->ink);
+	p->chain = pels.chain;
+	p->kformat = pels.kformat;
+	p->fill_ready = pels.fill_ready;
+	memcpy(p->ink, pels.ink, sizeof(p->ink));
+	memcpy(p->fill, pels.fill, sizeof(p->fill));
 	return p.release();
 }
 
@@ -371,8 +425,8 @@ void vips_hip_affine_need(const VipsHipAffinePlan *plan, int left, int top, int 
 		return;
 	const int off = plan->window_offset + 1;
 	int x0, x1, y0, y1;
-	axis_to_image(plan->args.extend, off, plan->width, e.left, e.left + e.width - 1, &x0, &x1);
-	axis_to_image(plan->args.extend, off, plan->height, e.top, e.top + e.height - 1, &y0, &y1);
+	embedded_axis_to_image(plan->args.extend, off, plan->width, e.left, e.left + e.width - 1, &x0, &x1);
+	embedded_axis_to_image(plan->args.extend, off, plan->height, e.top, e.top + e.height - 1, &y0, &y1);
 	in[0] = x0;
 	in[1] = y0;
 	in[2] = x1 - x0 + 1;
@@ -430,17 +484,12 @@ int vips_hip_affine_gen(VipsHipAffinePlan *plan, const VipsHipRegion *in, const 
 	{
 		std::lock_guard<std::mutex> lock(plan->mutex);
 		if (!plan->fill_ready) {
-			ImageRef one(vips_hip_image_new_from_memory(plan->fill, 1, 1, plan->bands, plan->format, plan->interpretation));
-			ImageRef pre;
-			if (!one.im || vips_hip_premultiply(one.im, &pre.im, 0))
+			ResamplePels pels;
+			pels.fill_ready = false;
+			memcpy(pels.fill, plan->fill, sizeof(pels.fill));
+			if (resample_fill_premultiply(domain, &pels, plan->bands, plan->format, plan->interpretation))
 				return -1;
-			if (pre.im->format != VIPS_HIP_FORMAT_FLOAT) {
-				error(domain, "premultiply did not make a float image");
-				return -1;
-			}
-			memset(plan->fill, 0, sizeof(plan->fill));
-			if (vips_hip_image_write_to_memory(pre.im, plan->fill))
-				return -1;
+			memcpy(plan->fill, pels.fill, sizeof(plan->fill));
 			plan->fill_ready = true;
 		}
 	}

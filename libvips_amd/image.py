@@ -494,6 +494,44 @@ class Image(object):
     def rotate(self, angle, **kwargs):
         return self._unary(lib.vips_hip_rotate, float(angle), ctypes.byref(self.affine_args(**kwargs)))
 
+    # vips_mapim and vips_xyz, with pyvips' argument names
+    @staticmethod
+    def mapim_args(interpolate="bilinear", extend="background", background=0, premultiplied=False):
+        """The VipsHipMapim of these arguments."""
+        args = _ffi.Mapim()
+        lib.vips_hip_mapim_defaults(ctypes.byref(args))
+        if isinstance(interpolate, str) and interpolate.lower() not in INTERPOLATORS:
+            raise _ffi.VipsHipError("mapim: interpolator %s is outside the HIP path (nearest, bilinear, bicubic)"
+                                    % interpolate)
+        args.interpolate = _enum(INTERPOLATORS, interpolate, "interpolate")
+        args.extend = _enum(EXTENDS, extend, "extend")
+        if background is not None:
+            background = [float(v) for v in np.atleast_1d(background)]
+            if len(background) > _ffi.Mapim.MAX_BACKGROUND:
+                raise _ffi.VipsHipError("mapim: background of more than %d elements" % _ffi.Mapim.MAX_BACKGROUND)
+            args.n_background = len(background)
+            args.background[:len(background)] = background
+        args.premultiplied = int(bool(premultiplied))
+        return args
+
+    def mapim(self, index, interpolate="bilinear", extend="background", background=0, premultiplied=False):
+        """vips_mapim: pel (x, y) of the result is this image resampled at the coordinate pel (x, y) of ``index`` holds
+        (two bands, or one complex band); the result has the index's size.  interpolate "nearest" / "bilinear" /
+        "bicubic"; extend, background and premultiplied as in pyvips."""
+        if not isinstance(index, Image):
+            raise TypeError("mapim: the index must be an Image")
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_mapim(self._h, index._h, ctypes.byref(out),
+                                 ctypes.byref(self.mapim_args(interpolate, extend, background, premultiplied))))
+        return Image(out.value)
+
+    @classmethod
+    def xyz(cls, width, height):
+        """vips_xyz: a two-band uint image whose pel (x, y) holds (x, y), made on the device."""
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_xyz(ctypes.byref(out), int(width), int(height)))
+        return cls(out.value)
+
     # vips_embed / vips_gravity / vips_flatten / vips_addalpha / vips_insert / vips_join, with pyvips' argument names
     @staticmethod
     def _background(args, background, what):
