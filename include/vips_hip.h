@@ -1086,6 +1086,35 @@ VIPS_HIP_API int vips_hip_mapim_step(int what);
  * (x, y), made on the device. */
 VIPS_HIP_API int vips_hip_xyz(VipsHipImage **out, int width, int height);
 
+/* ------------------------------------------------ template matching: fastcor, spcor
+ *
+ * vips_fastcor and vips_spcor (convolution/fastcor.c, spcor.c, correlation.c): @ref is slid over @in.  @out has the size
+ * and the interpretation of @in (of @ref where a one-band @in is matched to its bands); the two are brought to a
+ * common format (vips__formatalike) and to common bands (vips__bandalike: one band against n, "not one band or n
+ * bands" otherwise).  @in is extended by copies of its edges and
+ * sits at (ref.width / 2, ref.height / 2) of a canvas of in.size + ref.size - 1: output pel (x, y) compares @ref with
+ * the window of that canvas whose top-left corner is (x, y).  The canvas is not made.
+ *   fastcor: the sum of squared differences.  uint for integer images (the sum modulo 2^32), float for float, double for
+ *            double (sum = sum + dif * dif in the type, rows of the ref, then columns).
+ *   spcor:   the normalised correlation coefficient, always float, in the reference's doubles and in its order; +0 where
+ *            the ref or the window is constant.
+ * Bit-identical to the reference.  Complex images are refused, and a ref wider or taller than
+ * VIPS_HIP_CORRELATION_MAX_SIDE pels (whatever the format and the band count): what the kernels' LDS tile and ref
+ * table hold. */
+#define VIPS_HIP_CORRELATION_MAX_SIDE 64
+VIPS_HIP_API int vips_hip_fastcor(VipsHipImage *in, VipsHipImage *ref, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_spcor(VipsHipImage *in, VipsHipImage *ref, VipsHipImage **out);
+/* The per-band constants of vips_spcor (spcor.c:99-152) of a ref in host memory, after format matching: @pixels holds
+ * @height rows of @width pels of @bands elements of @format (non-complex), @stride bytes apart; @out_bands is the band
+ * count after band matching (@bands, or anything when @bands is 1: the one band is replicated).  rmean[b] is vips_avg
+ * of band b; c1[b] = sqrt(avg((float) (ref - rmean)^2) * N) through vips_linear's float output (its single-constant
+ * loop when all means are equal), double for a double ref.  @rmean and @c1 take @out_bands doubles.  No device is
+ * needed. */
+VIPS_HIP_API int vips_hip_spcor_constants(const void *pixels, int width, int height, int bands, int format, size_t stride,
+	int out_bands, double *rmean, double *c1);
+/* The kernels' units: 0 / 1 the pels / rows of a block's tile, 2 VIPS_HIP_CORRELATION_MAX_SIDE; 0 for anything else. */
+VIPS_HIP_API int vips_hip_correlation_step(int what);
+
 /* ------------------------------------------------ canvas and alpha: embed / gravity / insert / join, flatten, addalpha
  *
  * vips_embed and vips_gravity (conversion/embed.c), vips_insert (insert.c) and vips_join (join.c): exact copies of
@@ -1284,6 +1313,8 @@ VIPS_HIP_API int vips_hip_avg(VipsHipImage *in, double *out);
 VIPS_HIP_API int vips_hip_deviate(VipsHipImage *in, double *out);
 VIPS_HIP_API int vips_hip_min(VipsHipImage *in, double *out, int *x, int *y);
 VIPS_HIP_API int vips_hip_max(VipsHipImage *in, double *out, int *x, int *y);
+/* ... vips_hip_min and vips_hip_max take uint and int images too (their kernels compare in the image's own type): the
+ * place of the best match in what vips_hip_fastcor writes is found without leaving the device. */
 /* 0: the threads of a block of the arithmetic kernels; 1: the bytes of a group of the streaming kernels (of the output
  * for the pointwise kernels, of one band's share of the input for stats); 2 / 3: the most blocks a pointwise / a stats
  * launch has -- for tests that want sizes round them. */

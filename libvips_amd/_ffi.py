@@ -415,6 +415,11 @@ _SIGNATURES = {
     "vips_hip_mapim_gen": (c_int, [RegionP, RegionP, RegionP, P(Mapim), c_int, c_int]),
     "vips_hip_mapim_step": (c_int, [c_int]),
     "vips_hip_xyz": (c_int, [P(c_void_p), c_int, c_int]),
+    # fastcor, spcor
+    "vips_hip_fastcor": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_spcor": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_spcor_constants": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.c_size_t, c_int, P(c_double), P(c_double)]),
+    "vips_hip_correlation_step": (c_int, [c_int]),
     # embed / gravity / insert / join, flatten, addalpha
     "vips_hip_embed_defaults": (None, [P(Embed)]),
     "vips_hip_flatten_defaults": (None, [P(Flatten)]),

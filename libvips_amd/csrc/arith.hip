@@ -261,6 +261,8 @@ struct StatsAcc {
 		sum += v;
 		if constexpr (std::is_floating_point<T>::value)
 			sum2 += (double) v * (double) v;
+		else if constexpr (sizeof(T) == 4) // (uint, int: vips_min and vips_max only, the sums are not used)
+			sum2 += (unsigned long long) (long long) v * (unsigned long long) (long long) v;
 		else
 			sum2 += (unsigned long long) ((long long) v * (long long) v);
 		if (imx == STATS_NONE ? v == v : v > mx) {
@@ -476,6 +478,8 @@ int stats_run(const char *domain, const _VipsHipImage *in, StatsPartial *slab)
 	case VIPS_HIP_FORMAT_CHAR: return stats_launch<s8>(domain, in, a);
 	case VIPS_HIP_FORMAT_USHORT: return stats_launch<u16>(domain, in, a);
 	case VIPS_HIP_FORMAT_SHORT: return stats_launch<s16>(domain, in, a);
+	case VIPS_HIP_FORMAT_UINT: return stats_launch<u32>(domain, in, a);
+	case VIPS_HIP_FORMAT_INT: return stats_launch<s32>(domain, in, a);
 	case VIPS_HIP_FORMAT_FLOAT: return stats_launch<f32>(domain, in, a);
 	default:
 		error(domain, "no kernel for format %d", in->format);

@@ -351,6 +351,22 @@ int xyz_run(const char *domain, unsigned char *out, long long out_stride, int wi
 // mapim_tile: 0 / 1 the pels / rows of a block's patch, 2 / 3 of a wave's, 4 the most blocks a bounds launch has,
 // 5 the threads of a block of the bounds and xyz kernels, 6 the bytes of a group of the xyz kernel
 int mapim_tile(int what);
+// correlation.hip: vips_fastcor and vips_spcor on checked images of one format (ops_correlation.cpp checks everything): ONE
+// launch writes the whole output, width x height pels of `bands` elements.  Output band b reads band b of an operand of
+// `bands` bands and band 0 of an operand of one.  spcor: `table` holds bands * ref_w * ref_h doubles, band-major, the
+// ref's (rp - rmean[b]) in raster order, and c1 the bands doubles of spcor.c:146-149; both device memory.
+struct CorrelationArgs {
+	const unsigned char *in, *ref;
+	unsigned char *out;
+	const double *table, *c1;
+	long long in_stride, ref_stride, out_stride; // bytes
+	int width, height;                           // of the image and of the output
+	int in_bands, ref_bands, bands;
+	int ref_w, ref_h;
+};
+int correlation_run(const char *domain, CorrelationArgs a, int format, int spcor);
+// correlation_tile: 0 / 1 the pels / rows of a block's tile, 2 the largest ref side
+int correlation_tile(int what);
 // canvas.hip: vips_embed, vips_gravity, vips_insert and vips_join on checked geometry (ops_canvas.cpp checks everything):
 // ONE launch writes the rect (out_left, out_top, out_width, out_height) of a canvas.  Canvas pel (X, Y) is the sub-image's
 // pel where the sub-image lies, else the main image's pel where that lies, else -- by `mode` -- the ink, or the main

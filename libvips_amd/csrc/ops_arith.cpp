@@ -239,7 +239,9 @@ T from_bits(unsigned int bits)
 // a partial's extreme as the double the reference's matrix holds
 double value_of(int format, unsigned int bits)
 {
-	return format == VIPS_HIP_FORMAT_FLOAT ? (double) from_bits<float>(bits) : (double) from_bits<int>(bits);
+	if (format == VIPS_HIP_FORMAT_FLOAT)
+		return (double) from_bits<float>(bits);
+	return format == VIPS_HIP_FORMAT_UINT ? (double) bits : (double) from_bits<int>(bits);
 }
 
 // the slab's partials of one band, blocks in index order, to row b + 1 of the matrix
@@ -291,7 +293,8 @@ void merge_band(const StatsPartial *slab, int blocks, int bands, int b, int form
 	row[COL_YMAX] = imx == STATS_NONE ? 0 : (double) (imx / (unsigned int) width);
 }
 
-int stats_matrix(const char *domain, VipsHipImage *in, std::vector<double> *matrix)
+// extremes: the call wants only the extremes and their places (vips_min, vips_max), which uint and int images have too
+int stats_matrix(const char *domain, VipsHipImage *in, std::vector<double> *matrix, bool extremes = false)
 {
 	if (in && bind_to(in)) // run where the pixels live
 		return -1;
@@ -308,7 +311,17 @@ int stats_matrix(const char *domain, VipsHipImage *in, std::vector<double> *matr
 	case VIPS_HIP_FORMAT_SHORT:
 	case VIPS_HIP_FORMAT_FLOAT:
 		break;
+	case VIPS_HIP_FORMAT_UINT:
+	case VIPS_HIP_FORMAT_INT:
+		if (extremes)
+			break;
+		error(domain, "uint, int and double images are outside the HIP path (uchar, char, ushort, short and float only)");
+		return -1;
 	default:
+		if (extremes) {
+			error(domain, "double images are outside the HIP path (uchar, char, ushort, short, uint, int and float only)");
+			return -1;
+		}
 		error(domain, "uint, int and double images are outside the HIP path (uchar, char, ushort, short and float only)");
 		return -1;
 	}
@@ -627,7 +640,7 @@ int vips_hip_min(VipsHipImage *in, double *out, int *x, int *y)
 		error("min", "null argument");
 		return -1;
 	}
-	if (stats_matrix("min", in, &matrix))
+	if (stats_matrix("min", in, &matrix, true))
 		return -1;
 	*out = matrix[COL_MIN];
 	if (x)
@@ -644,7 +657,7 @@ int vips_hip_max(VipsHipImage *in, double *out, int *x, int *y)
 		error("max", "null argument");
 		return -1;
 	}
-	if (stats_matrix("max", in, &matrix))
+	if (stats_matrix("max", in, &matrix, true))
 		return -1;
 	*out = matrix[COL_MAX];
 	if (x)

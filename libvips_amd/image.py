@@ -525,6 +525,22 @@ class Image(object):
                                  ctypes.byref(self.mapim_args(interpolate, extend, background, premultiplied))))
         return Image(out.value)
 
+    # libvips/convolution: vips_fastcor / vips_spcor
+    def fastcor(self, ref):
+        """vips_fastcor: the sum of squared differences between ``ref`` and the window of this image at every pel (uint,
+        float or double; the image is extended by copies of its edges and shifted by half the ref).  The best match is
+        ``fastcor(ref).min(with_options=True)``."""
+        if not isinstance(ref, Image):
+            raise TypeError("fastcor: the ref must be an Image")
+        return self._binary(lib.vips_hip_fastcor, ref)
+
+    def spcor(self, ref):
+        """vips_spcor: the normalised correlation coefficient of ``ref`` and the window of this image at every pel, a
+        float image; 0 where the ref or the window is constant."""
+        if not isinstance(ref, Image):
+            raise TypeError("spcor: the ref must be an Image")
+        return self._binary(lib.vips_hip_spcor, ref)
+
     @classmethod
     def xyz(cls, width, height):
         """vips_xyz: a two-band uint image whose pel (x, y) holds (x, y), made on the device."""
