@@ -3001,3 +3001,273 @@ static void
 vips_bandbool_hip_init(VipsBandboolHip *logic)
 {
 }
+
+/* replicate_hip, wrap_hip, grid_hip (conversion/replicate.c, wrap.c, grid.c) and zoom_hip, subsample_hip (zoom.c,
+ * subsample.c).  The header is the original's (hip_twin_header: wrap's Xoffset / Yoffset come with it, and its build
+ * has said "bad grid geometry", "zoom factors too large" or "image has shrunk to nothing" by then).  The region forms
+ * work in whole-image coordinates; a strip reads the rows vips_hip_replicate_need / vips_hip_grid_need name, which is
+ * every row once a strip crosses a period or a grid has more than one tile across.  wrap_hip is vips_hip_replicate_gen
+ * with the offset.  (arrayjoin takes an array of images and these classes take one: it has no class here.) */
+typedef struct _VipsCellsHip {
+	VipsHipOp parent_instance;
+	int across, down, tile_height;
+	int x, y;
+	int xfac, yfac;
+	gboolean point;
+} VipsCellsHip;
+
+typedef VipsCellsHip VipsReplicateHip;
+typedef VipsCellsHip VipsWrapHip;
+typedef VipsCellsHip VipsGridHip;
+typedef VipsCellsHip VipsZoomHip;
+typedef VipsCellsHip VipsSubsampleHip;
+
+static int
+vips_cells_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	/* the arguments are the plan */
+	*plan = op;
+
+	return 0;
+}
+
+static void
+vips_cells_hip_strip_close(VipsHipOp *op, void *plan)
+{
+}
+
+static int
+vips_replicate_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_replicate(in, out, cells->across, cells->down);
+}
+
+/* Where the output's pel (0, 0) lies in its period: for wrap_hip what the original's build put into the header
+ * (wrap.c:99-100), for replicate_hip the corner. */
+static void
+cells_hip_origin(VipsHipOp *op, int *x0, int *y0)
+{
+	const gboolean wrap = strcmp(VIPS_OBJECT_GET_CLASS(op)->nickname, "wrap_hip") == 0;
+
+	*x0 = wrap ? op->out->Xoffset : 0;
+	*y0 = wrap ? op->out->Yoffset : 0;
+}
+
+static void
+vips_replicate_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	int x0, y0, need[4];
+
+	cells_hip_origin(op, &x0, &y0);
+	vips_hip_replicate_need(op->ready->Xsize, op->ready->Ysize, x0, y0, 0, out_top, op->out->Xsize, out_rows, need);
+	*in_top = need[1];
+	*in_rows = need[3];
+}
+
+static int
+vips_replicate_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	int x0, y0;
+
+	cells_hip_origin(op, &x0, &y0);
+
+	return vips_hip_replicate_gen(x0, y0, in, out);
+}
+
+static int
+vips_wrap_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_wrap(in, out, cells->x, cells->y, vips_object_argument_isset(VIPS_OBJECT(op), "x"),
+		vips_object_argument_isset(VIPS_OBJECT(op), "y"));
+}
+
+static int
+vips_grid_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_grid(in, out, cells->tile_height, cells->across, cells->down);
+}
+
+static void
+vips_grid_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+	int need[4];
+
+	vips_hip_grid_need(op->ready->Xsize, op->ready->Ysize, cells->tile_height, cells->across, 0, out_top, op->out->Xsize,
+		out_rows, need);
+	*in_top = need[1];
+	*in_rows = need[3];
+}
+
+static int
+vips_grid_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_grid_gen(cells->tile_height, cells->across, in, out);
+}
+
+static int
+vips_zoom_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_zoom(in, out, cells->xfac, cells->yfac);
+}
+
+static void
+vips_zoom_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	*in_top = out_top / cells->yfac;
+	*in_rows = (out_top + out_rows - 1) / cells->yfac - *in_top + 1;
+}
+
+static int
+vips_zoom_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_zoom_gen(in, out, cells->xfac, cells->yfac);
+}
+
+static int
+vips_subsample_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_subsample(in, out, cells->xfac, cells->yfac);
+}
+
+static void
+vips_subsample_hip_strip_need(VipsHipOp *op, void *plan, int out_top, int out_rows, int *in_top, int *in_rows)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	*in_top = out_top * cells->yfac;
+	*in_rows = (out_rows - 1) * cells->yfac + 1;
+}
+
+static int
+vips_subsample_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsCellsHip *cells = (VipsCellsHip *) op;
+
+	return vips_hip_subsample_gen(in, out, cells->xfac, cells->yfac);
+}
+
+#define vips_replicate_hip_strip_open vips_cells_hip_strip_open
+#define vips_replicate_hip_strip_close vips_cells_hip_strip_close
+#define vips_wrap_hip_strip_open vips_cells_hip_strip_open
+#define vips_wrap_hip_strip_need vips_replicate_hip_strip_need
+#define vips_wrap_hip_strip_run vips_replicate_hip_strip_run
+#define vips_wrap_hip_strip_close vips_cells_hip_strip_close
+#define vips_grid_hip_strip_open vips_cells_hip_strip_open
+#define vips_grid_hip_strip_close vips_cells_hip_strip_close
+#define vips_zoom_hip_strip_open vips_cells_hip_strip_open
+#define vips_zoom_hip_strip_close vips_cells_hip_strip_close
+#define vips_subsample_hip_strip_open vips_cells_hip_strip_open
+#define vips_subsample_hip_strip_close vips_cells_hip_strip_close
+
+HIP_SUBCLASS_FULL(VipsReplicateHip, vips_replicate_hip, "replicate_hip", "replicate an image (MI355X)", HIP_STRIPS(vips_replicate_hip))
+HIP_SUBCLASS_FULL(VipsWrapHip, vips_wrap_hip, "wrap_hip", "wrap image origin (MI355X)", HIP_STRIPS(vips_wrap_hip))
+HIP_SUBCLASS_FULL(VipsGridHip, vips_grid_hip, "grid_hip", "grid an image (MI355X)", HIP_STRIPS(vips_grid_hip))
+HIP_SUBCLASS_FULL(VipsZoomHip, vips_zoom_hip, "zoom_hip", "zoom an image (MI355X)", HIP_STRIPS(vips_zoom_hip))
+HIP_SUBCLASS_FULL(VipsSubsampleHip, vips_subsample_hip, "subsample_hip", "subsample an image (MI355X)", HIP_STRIPS(vips_subsample_hip))
+
+static void
+vips_replicate_hip_args(VipsReplicateHipClass *class)
+{
+	VIPS_ARG_INT(class, "across", 4, "Across", "Repeat this many times horizontally",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCellsHip, across), 1, 1000000, 1);
+	VIPS_ARG_INT(class, "down", 5, "Down", "Repeat this many times vertically",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCellsHip, down), 1, 1000000, 1);
+}
+
+static void
+vips_wrap_hip_args(VipsWrapHipClass *class)
+{
+	VIPS_ARG_INT(class, "x", 3, "x", "Left edge of input in output",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCellsHip, x), -VIPS_MAX_COORD, VIPS_MAX_COORD, 0);
+	VIPS_ARG_INT(class, "y", 4, "y", "Top edge of input in output",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCellsHip, y), -VIPS_MAX_COORD, VIPS_MAX_COORD, 0);
+}
+
+static void
+vips_grid_hip_args(VipsGridHipClass *class)
+{
+	VIPS_ARG_INT(class, "tile_height", 3, "Tile height", "Chop into tiles this high",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCellsHip, tile_height), 1, 10000000, 128);
+	VIPS_ARG_INT(class, "across", 4, "Across", "Number of tiles across",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCellsHip, across), 1, 10000000, 1);
+	VIPS_ARG_INT(class, "down", 5, "Down", "Number of tiles down",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCellsHip, down), 1, 10000000, 1);
+}
+
+static void
+cells_hip_factor_args(VipsHipOpClass *class)
+{
+	VIPS_ARG_INT(class, "xfac", 3, "Xfac", "Horizontal factor",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCellsHip, xfac), 1, VIPS_MAX_COORD, 1);
+	VIPS_ARG_INT(class, "yfac", 4, "Yfac", "Vertical factor",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsCellsHip, yfac), 1, VIPS_MAX_COORD, 1);
+}
+
+static void
+vips_zoom_hip_args(VipsZoomHipClass *class)
+{
+	cells_hip_factor_args(class);
+}
+
+static void
+vips_subsample_hip_args(VipsSubsampleHipClass *class)
+{
+	cells_hip_factor_args(class);
+	VIPS_ARG_BOOL(class, "point", 5, "Point", "Point sample",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsCellsHip, point), FALSE);
+}
+
+static void
+vips_cells_hip_init(VipsCellsHip *cells)
+{
+	cells->across = cells->down = 1;
+	cells->tile_height = 128;
+	cells->xfac = cells->yfac = 1;
+}
+
+static void
+vips_replicate_hip_init(VipsReplicateHip *cells)
+{
+	vips_cells_hip_init(cells);
+}
+
+static void
+vips_wrap_hip_init(VipsWrapHip *cells)
+{
+	vips_cells_hip_init(cells);
+}
+
+static void
+vips_grid_hip_init(VipsGridHip *cells)
+{
+	vips_cells_hip_init(cells);
+}
+
+static void
+vips_zoom_hip_init(VipsZoomHip *cells)
+{
+	vips_cells_hip_init(cells);
+}
+
+static void
+vips_subsample_hip_init(VipsSubsampleHip *cells)
+{
+	vips_cells_hip_init(cells);
+}

@@ -1444,12 +1444,15 @@ hip_copy_argument(VipsObject *object, GParamSpec *pspec, VipsArgumentClass *argu
 	GObject *twin = G_OBJECT(a);
 	const char *name = g_param_spec_get_name(pspec);
 
+	/* (vips_zoom and vips_subsample name their image argument "input") */
+	if (strcmp(name, "in") == 0 && !g_object_class_find_property(G_OBJECT_GET_CLASS(twin), "in"))
+		name = "input";
 	if ((argument_class->flags & VIPS_ARGUMENT_INPUT) && argument_instance->assigned &&
 		g_object_class_find_property(G_OBJECT_GET_CLASS(twin), name)) {
 		GValue value = G_VALUE_INIT;
 
 		g_value_init(&value, G_PARAM_SPEC_VALUE_TYPE(pspec));
-		g_object_get_property(G_OBJECT(object), name, &value);
+		g_object_get_property(G_OBJECT(object), g_param_spec_get_name(pspec), &value);
 		g_object_set_property(twin, name, &value);
 		g_value_unset(&value);
 	}
@@ -1556,7 +1559,7 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *   - affine / similarity / rotate of double images, with an interpolator other than nearest, bilinear and bicubic
  *     (lbb, nohalo, vsqbs), and of pels of more than 16 bands;
  *   - embed / gravity of pels of more than 32 bytes (the canvas kernels' ink), flatten to a background of more than
- *     256 bytes;
+ *     256 bytes; replicate / wrap / grid of pels of more than 32 bytes (the cells kernels' pel);
  *   - linear with a vector of more than VIPS_HIP_ARITH_MAX_VECTOR elements (what the kernels keep in LDS);
  *   - relational_const / boolean_const of more than VIPS_HIP_LOGIC_MAX_VECTOR bands or constants, bandjoin_const of no
  *     constants or of VIPS_HIP_BANDJOIN_MAX and more (the band kernel's source table).
@@ -1613,6 +1616,9 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 			return TRUE;
 	}
 	if ((strcmp(nick, "embed_hip") == 0 || strcmp(nick, "gravity_hip") == 0) && VIPS_IMAGE_SIZEOF_PEL(in) > 32)
+		return TRUE;
+	if ((strcmp(nick, "replicate_hip") == 0 || strcmp(nick, "wrap_hip") == 0 || strcmp(nick, "grid_hip") == 0) &&
+		VIPS_IMAGE_SIZEOF_PEL(in) > 32)
 		return TRUE;
 	if (strcmp(nick, "flatten_hip") == 0 && in->Bands > 1 &&
 		(guint64) (in->Bands - 1) * VIPS_MAX(VIPS_IMAGE_SIZEOF_ELEMENT(in), sizeof(double)) > 256)
@@ -1777,7 +1783,7 @@ vips_hip_op_init(VipsHipOp *op)
 
 /* ------------------------------------------------------------------ subclasses */
 
-/* (the 36 operation classes: arguments, defaults, hooks) */
+/* (the operation classes: arguments, defaults, hooks) */
 #include "vips_hip_classes.c"
 
 /* ------------------------------------------------------------------ registration */
@@ -1833,6 +1839,11 @@ g_module_check_init(GModule *module)
 	vips_extract_band_hip_get_type();
 	vips_bandmean_hip_get_type();
 	vips_bandbool_hip_get_type();
+	vips_replicate_hip_get_type();
+	vips_wrap_hip_get_type();
+	vips_grid_hip_get_type();
+	vips_zoom_hip_get_type();
+	vips_subsample_hip_get_type();
 
 	/* types registered by a module must never be unloaded */
 	g_module_make_resident(module);

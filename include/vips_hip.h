@@ -1227,6 +1227,78 @@ VIPS_HIP_API int vips_hip_join(VipsHipImage *in1, VipsHipImage *in2, VipsHipImag
  * (0: that pel size takes the one-pel-a-lane kernel), for tests that want sizes round them. */
 VIPS_HIP_API int vips_hip_canvas_step(int what, int pel_size);
 
+/* ------------------------------------------------ sheets and tiles: arrayjoin, replicate, wrap, grid; zoom, subsample
+ *
+ * vips_arrayjoin (conversion/arrayjoin.c), vips_replicate (replicate.c), vips_wrap (wrap.c) and vips_grid (grid.c):
+ * exact copies of pels into a lattice of cells, ONE launch an operation (cells.hip) that writes every output byte once,
+ * any non-complex format, pels of up to 32 bytes.  vips_zoom (zoom.c) and vips_subsample (subsample.c) as whole-image
+ * calls over vips_hip_zoom_gen / vips_hip_subsample_gen.  Complex images are refused with "image must be non-complex".
+ * Results carry no orientation.
+ */
+
+/* The optional arguments of vips_arrayjoin.  @across, @hspacing, @vspacing 0: not given (n images across; the widest
+ * and the tallest image).  @halign / @valign: a VipsAlign (0 low, 1 centre, 2 high).  @n_background 0: not given (one
+ * zero). */
+typedef struct {
+	int across;
+	int shim;
+	int n_background;
+	double background[VIPS_HIP_CANVAS_MAX_BACKGROUND];
+	int halign, valign;
+	int hspacing, vspacing;
+} VipsHipArrayjoin;
+VIPS_HIP_API void vips_hip_arrayjoin_defaults(VipsHipArrayjoin *args);
+
+/* The geometry of vips_arrayjoin_build (arrayjoin.c:231-355) for @n images of widths[i] x heights[i], on plain ints:
+ * the output's size, the images across, rects[4 i ..]: left, top, width, height of image i's rect on the output (wider
+ * by the shim except in the last column and row; the last image's reaches the right edge), offsets[2 i ..]: where
+ * image i's pel (0, 0) lies in its rect -- negative where the image is larger than the spacing and so is cropped, as
+ * the reference's vips_embed crops it.  No device is touched. */
+VIPS_HIP_API int vips_hip_arrayjoin_plan(const VipsHipArrayjoin *args, int n, const int *widths, const int *heights,
+	int *out_width, int *out_height, int *across, int *rects, int *offsets);
+/* vips_arrayjoin_build (arrayjoin.c:182-373): vips__formatalike_vec (vips_hip_cast to the common format), then
+ * vips__bandalike_vec with the background's length counted in (a one-band image becomes n bands), then one launch over
+ * a table of n descriptors.  Output pel (X, Y) is image min(n - 1, X / (hspacing + shim) + Y / (vspacing + shim) *
+ * across)'s (arrayjoin.c:119,145: an incomplete last row is filled from the last image's stretched rect) or the
+ * background.  All images must be on one device. */
+VIPS_HIP_API int vips_hip_arrayjoin(VipsHipImage **in, int n, VipsHipImage **out, const VipsHipArrayjoin *args);
+
+/* vips_replicate_build (replicate.c:140-180): @across x @down copies, each 1 .. 1000000. */
+VIPS_HIP_API int vips_hip_replicate(VipsHipImage *in, VipsHipImage **out, int across, int down);
+/* vips_wrap_build (wrap.c:65-103): pel (X, Y) is pel ((X + x') mod width, (Y + y') mod height) with the reference's
+ * clock arithmetic for x' and y' (x' is the WIDTH when @x is a positive multiple of it).  @x_set / @y_set 0: the
+ * defaults, width / 2 and height / 2. */
+VIPS_HIP_API int vips_hip_wrap(VipsHipImage *in, VipsHipImage **out, int x, int y, int x_set, int y_set);
+/* vips_grid_build (grid.c:148-183): a strip of across * down tiles of @tile_height rows becomes a grid; "bad grid
+ * geometry" when the strip's height is not tile_height * across * down. */
+VIPS_HIP_API int vips_hip_grid(VipsHipImage *in, VipsHipImage **out, int tile_height, int across, int down);
+
+/* The rows of the input that an output rect draws on, need[4] = left, top, width, height: the bounding box of the pels
+ * read.  On an axis where the rect crosses a period of a replicate that is the image's WHOLE width or height (the box
+ * of a wrapped interval is everything).  For a grid it is the rows from the first tile touched to the last one: with
+ * more than one tile across, a rect that spans tiles draws on tiles that lie far apart in the strip, so a row of the
+ * grid needs (across - 1) * tile_height + 1 rows of it, and every column.  That is the honest answer: a bounding box
+ * cannot say less.  @x0, @y0: where the output's pel (0, 0) lies in its period (0 for vips_replicate). */
+VIPS_HIP_API void vips_hip_replicate_need(int in_width, int in_height, int x0, int y0, int left, int top, int width,
+	int height, int need[4]);
+VIPS_HIP_API void vips_hip_grid_need(int in_width, int in_height, int tile_height, int across, int left, int top,
+	int width, int height, int need[4]);
+/* Fill @out, a window of the output (im_width x im_height its size), from @in, a window of the input image that must
+ * hold the need of the rect ("input region too small" otherwise).  Bytes of @out's frame outside the window are not
+ * touched.  Both regions' memory must cover height * stride bytes from `data` (see vips_hip_embed_gen).
+ * vips_wrap is vips_hip_replicate_gen with the image's Xoffset / Yoffset as @x0 / @y0. */
+VIPS_HIP_API int vips_hip_replicate_gen(int x0, int y0, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_grid_gen(int tile_height, int across, const VipsHipRegion *in, const VipsHipRegion *out);
+
+/* vips_zoom_build (zoom.c:309-353): "zoom factors too large" when a side would pass INT_MAX / 2; factors of 1 are a
+ * copy.  vips_subsample_build (subsample.c:193-247): sizes round down, "image has shrunk to nothing"; the reference's
+ * `point` picks between two loops that make the same pels, so there is nothing to pass. */
+VIPS_HIP_API int vips_hip_zoom(VipsHipImage *in, VipsHipImage **out, int xfac, int yfac);
+VIPS_HIP_API int vips_hip_subsample(VipsHipImage *in, VipsHipImage **out, int xfac, int yfac);
+/* 0: the threads of a block of the cells kernels; 1: the bytes of a group of the streaming kernel for @pel_size
+ * (0: that pel size takes the one-pel-a-lane kernel), for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_cells_step(int what, int pel_size);
+
 /* ------------------------------------------------ arithmetic: linear / invert / abs, add / subtract / multiply / divide,
  * stats / avg / deviate / min / max
  *

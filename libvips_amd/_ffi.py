@@ -135,6 +135,22 @@ class Insert(ctypes.Structure):
     ]
 
 
+class Arrayjoin(ctypes.Structure):
+    """VipsHipArrayjoin (include/vips_hip.h): the optional arguments of vips_arrayjoin."""
+
+    MAX_BACKGROUND = 32
+    _fields_ = [
+        ("across", ctypes.c_int),
+        ("shim", ctypes.c_int),
+        ("n_background", ctypes.c_int),
+        ("background", ctypes.c_double * 32),
+        ("halign", ctypes.c_int),
+        ("valign", ctypes.c_int),
+        ("hspacing", ctypes.c_int),
+        ("vspacing", ctypes.c_int),
+    ]
+
+
 class Linear(ctypes.Structure):
     """VipsHipLinear (include/vips_hip.h): the arguments of vips_linear."""
 
@@ -438,6 +454,20 @@ _SIGNATURES = {
     "vips_hip_insert": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, c_int, P(Insert)]),
     "vips_hip_join": (c_int, [c_void_p, c_void_p, P(c_void_p), c_int, P(Insert)]),
     "vips_hip_canvas_step": (c_int, [c_int, c_int]),
+    # arrayjoin / replicate / wrap / grid, zoom / subsample
+    "vips_hip_arrayjoin_defaults": (None, [P(Arrayjoin)]),
+    "vips_hip_arrayjoin_plan": (c_int, [P(Arrayjoin), c_int, P(c_int), P(c_int), P(c_int), P(c_int), P(c_int), P(c_int), P(c_int)]),
+    "vips_hip_arrayjoin": (c_int, [P(c_void_p), c_int, P(c_void_p), P(Arrayjoin)]),
+    "vips_hip_replicate": (c_int, [c_void_p, P(c_void_p), c_int, c_int]),
+    "vips_hip_wrap": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, c_int]),
+    "vips_hip_grid": (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int]),
+    "vips_hip_replicate_need": (None, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P(c_int)]),
+    "vips_hip_grid_need": (None, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P(c_int)]),
+    "vips_hip_replicate_gen": (c_int, [c_int, c_int, RegionP, RegionP]),
+    "vips_hip_grid_gen": (c_int, [c_int, c_int, RegionP, RegionP]),
+    "vips_hip_zoom": (c_int, [c_void_p, P(c_void_p), c_int, c_int]),
+    "vips_hip_subsample": (c_int, [c_void_p, P(c_void_p), c_int, c_int]),
+    "vips_hip_cells_step": (c_int, [c_int, c_int]),
     # linear / invert / abs, add / subtract / multiply / divide, stats / avg / deviate / min / max
     "vips_hip_linear_defaults": (None, [P(Linear)]),
     "vips_hip_arith_format": (c_int, [c_int, c_int]),

@@ -408,6 +408,43 @@ int flatten_run(const char *domain, FlattenArgs a, int format);
 // ... vips_addalpha: every pel's `bands` elements of `es` bytes, then `alpha` (the low es bytes)
 int addalpha_run(const char *domain, const unsigned char *in, long long in_stride, unsigned char *out, long long out_stride,
 	int width, int height, int bands, int es, unsigned long long alpha);
+// ops_canvas.cpp: vips__bandup (arithmetic.c:175-202) of a one-band image, the result tagged `interpretation`
+int bandup(_VipsHipImage *in, _VipsHipImage **out, int n, int interpretation);
+// cells.hip: vips_arrayjoin, vips_replicate, vips_wrap and vips_grid on checked geometry (ops_cells.cpp checks everything):
+// ONE launch writes the rect (out_left, out_top, out_width, out_height) of an output that is a lattice of cells of
+// cell_w x cell_h pels.  Output pel (X, Y) lies in cell (cx, cy) = ((X + org_x) / cell_w, (Y + org_y) / cell_h); a cell
+// shows pels of one source row or the ink.  Which source:
+//   CELLS_TABLE   descriptor min(n - 1, cx + cy * across) of `table` (arrayjoin.c:119,145): image pel (X - x0, Y - y0)
+//                 where the image has one, else the ink
+//   CELLS_REPEAT  the cell is one period of `src` (org_x, org_y in [0, sw] x [0, sh]: where the output's pel (0, 0) lies
+//                 in its period): pel ((X + org_x) mod sw, (Y + org_y) mod sh)
+//   CELLS_GRID    cell (cx, cy) is rows (cy * across + cx) * cell_h ... of `src` (grid.c:103,136)
+// `src` points at pel (win_left, win_top) of the image of sw x sh pels.
+enum { CELLS_TABLE = 0, CELLS_REPEAT = 1, CELLS_GRID = 2 };
+struct CellDesc {
+	const unsigned char *base; // the image's pel (0, 0)
+	long long stride;          // bytes
+	int x0, y0;                // where that pel lies on the output: negative steps into a cell where the image is cropped
+	int w, h;                  // the image
+};
+struct CellsArgs {
+	const CellDesc *table; // CELLS_TABLE: n descriptors in device memory
+	const unsigned char *src;
+	unsigned char *out; // pel (out_left, out_top) of the output
+	long long src_stride, out_stride; // bytes
+	int mode;                         // CELLS_*
+	int n, across;
+	int cell_w, cell_h, org_x, org_y;
+	int sw, sh, win_left, win_top;
+	int out_left, out_top, out_width, out_height;
+	int pel;    // bytes
+	int groups; // (stream kernel) 16- / 48-byte groups of a row of the rect, the ragged one included
+	unsigned int ink[CANVAS_MAX_PEL / 4];
+};
+// `starts`: every source's base and stride or-ed together (what the row starts of all sources are multiples of)
+int cells_run(const char *domain, CellsArgs a, unsigned long long starts);
+// cells_tile: as canvas_tile
+int cells_tile(int what, int pel);
 // pointwise.h: the geometry of a pointwise launch on checked operands: ONE launch writes `height` rows of `elems` output
 // elements.  Output element e of row y is made from element e of the operand's row, or -- an operand of one element a
 // pel (b1 / b2 == 1) against `bands` -- from element e / bands; an operand is zero right of its w1 / w2 pels and below

@@ -189,24 +189,6 @@ int embed_image(const char *domain, VipsHipImage *in, VipsHipImage **out, int x,
 	return 0;
 }
 
-// vips__bandup (arithmetic.c:175-202) of a one-band image: every element n times, which is vips_zoom by n across of
-// the same elements
-int bandup(VipsHipImage *in, VipsHipImage **out, int n, int interpretation)
-{
-	ImageRef o(vips_hip_image_new(in->width, in->height, n, in->format, interpretation));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	ro.bands = 1;
-	ro.width = ro.im_width = in->width * n;
-	if (vips_hip_zoom_gen(&ri, &ro, n, 1))
-		return -1;
-	*out = o.release();
-	return 0;
-}
-
 // arithmetic.c:76-109
 int format_common(int a, int b)
 {
@@ -323,6 +305,24 @@ int insert_image(const char *domain, VipsHipImage *main, VipsHipImage *sub, Vips
 }
 
 } // namespace
+
+// vips__bandup (arithmetic.c:175-202) of a one-band image: every element n times, which is vips_zoom by n across of
+// the same elements
+int vh::bandup(VipsHipImage *in, VipsHipImage **out, int n, int interpretation)
+{
+	ImageRef o(vips_hip_image_new(in->width, in->height, n, in->format, interpretation));
+	if (!o.im)
+		return -1;
+	VipsHipRegion ri, ro;
+	vips_hip_image_region(in, &ri);
+	vips_hip_image_region(o.im, &ro);
+	ro.bands = 1;
+	ro.width = ro.im_width = in->width * n;
+	if (vips_hip_zoom_gen(&ri, &ro, n, 1))
+		return -1;
+	*out = o.release();
+	return 0;
+}
 
 extern "C" {
 

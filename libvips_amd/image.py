@@ -619,6 +619,56 @@ class Image(object):
                                 ctypes.byref(self._insert_args(expand, background, shim, align))))
         return Image(out.value)
 
+    # vips_arrayjoin / vips_replicate / vips_wrap / vips_grid / vips_zoom / vips_subsample, with pyvips' argument names
+    @classmethod
+    def arrayjoin_args(cls, across=None, shim=0, background=None, halign="low", valign="low", hspacing=None, vspacing=None):
+        """The VipsHipArrayjoin of these arguments: None means not given."""
+        args = _ffi.Arrayjoin()
+        lib.vips_hip_arrayjoin_defaults(ctypes.byref(args))
+        for name, value in (("across", across), ("hspacing", hspacing), ("vspacing", vspacing)):
+            if value is not None:
+                if int(value) < 1:
+                    raise _ffi.VipsHipError("arrayjoin: %s must be at least 1" % name)
+                setattr(args, name, int(value))
+        args.shim = int(shim)
+        args.halign = _enum(ALIGNS, halign, "halign")
+        args.valign = _enum(ALIGNS, valign, "valign")
+        return cls._background(args, background, "arrayjoin")
+
+    @staticmethod
+    def arrayjoin(images, across=None, shim=0, background=None, halign="low", valign="low", hspacing=None, vspacing=None):
+        """vips_arrayjoin: the images laid out as a grid ``across`` wide (default: one row), one launch for the whole
+        sheet.  Each image sits in a box of hspacing x vspacing (default: the largest image) by halign / valign; boxes
+        are ``shim`` apart; what no image covers is ``background``."""
+        images = list(images)
+        handles = (ctypes.c_void_p * max(1, len(images)))(*[im._h for im in images])
+        out = ctypes.c_void_p()
+        args = Image.arrayjoin_args(across, shim, background, halign, valign, hspacing, vspacing)
+        check(lib.vips_hip_arrayjoin(handles, len(images), ctypes.byref(out), ctypes.byref(args)))
+        return Image(out.value)
+
+    def replicate(self, across, down):
+        """vips_replicate: the image ``across`` times across and ``down`` times down."""
+        return self._unary(lib.vips_hip_replicate, int(across), int(down))
+
+    def wrap(self, x=None, y=None):
+        """vips_wrap: the image's origin moved to (x, y), what leaves at one side comes back at the other; the defaults
+        are the centre."""
+        return self._unary(lib.vips_hip_wrap, int(x or 0), int(y or 0), int(x is not None), int(y is not None))
+
+    def grid(self, tile_height, across, down):
+        """vips_grid: a tall strip of across * down tiles of ``tile_height`` rows laid out as a grid."""
+        return self._unary(lib.vips_hip_grid, int(tile_height), int(across), int(down))
+
+    def zoom(self, xfac, yfac):
+        """vips_zoom: every pel ``xfac`` times across and ``yfac`` times down."""
+        return self._unary(lib.vips_hip_zoom, int(xfac), int(yfac))
+
+    def subsample(self, xfac, yfac, point=False):
+        """vips_subsample: every ``xfac``-th pel of every ``yfac``-th row.  ``point`` picks between two loops of the
+        reference that make the same pels; it changes nothing here."""
+        return self._unary(lib.vips_hip_subsample, int(xfac), int(yfac))
+
     # vips_linear / vips_invert / vips_abs, vips_add / vips_subtract / vips_multiply / vips_divide, vips_stats and its
     # single-number siblings, with pyvips' argument names
     @staticmethod
