@@ -1124,7 +1124,7 @@ int conva_fast_image(const _VipsHipImage *in, _VipsHipImage *out, const _VipsHip
 }
 
 
-// Image-level halves used by ops_colour_conv.cpp.
+// Image-level halves used by ops_conv.cpp.
 
 // Both passes of a convasep through the fused separable kernel; 1 when not covered.
 int convasep_fused(const _VipsHipImage *in, _VipsHipImage *out, const _VipsHipConva *plan)

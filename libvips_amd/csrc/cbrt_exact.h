@@ -16,7 +16,7 @@
 // Entries below 886 are the table's linear arm, computed as the table code does.  The host makes
 // r[] by running THIS function (same operations, same order, IEEE double: identical on both
 // sides) against its own table and refuses the scheme if any entry does not come out: exact by
-// construction, checked entry by entry when the tables are made (colour.hip cbrt_exact_tables()).
+// construction, checked entry by entry when the tables are made (colour_tables.cpp cbrt_exact_tables()).
 #pragma once
 
 #include <cstdint>

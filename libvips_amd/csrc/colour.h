@@ -22,7 +22,7 @@ int colour_route(const int *steps, int n_steps, double alpha_scale, const VipsHi
 // device by the route's own steps, applied from LDS by one streaming kernel
 int grey_lut_image(const VipsHipRegion *in, const VipsHipRegion *out, bool to16);
 
-// vips_sharpen on a whole 3-band uchar sRGB image in one kernel (colour.hip); 1 = not its case
+// vips_sharpen on a whole 3-band uchar sRGB image in one kernel (colour_sharpen.h); 1 = not its case
 // (win: the part of the LUT that is not constant, as shorts on the device -- the kernel with every table in LDS;
 // nullptr: the kernel that reads the whole LUT through global memory)
 struct SharpenLutWindow {
@@ -54,5 +54,33 @@ int resize_sharpen_stream_u8_try(_VipsHipReduce *rv, int vshrink, _VipsHipReduce
 
 int premultiply_region(const VipsHipRegion *in, const VipsHipRegion *out, double max_alpha, int uchar,
 	int inverse);
+
+// ops_colour.cpp: one entry of vips_colour_routes[] (colourspace.c:223-520), restricted to the spaces of this
+// library: the colour steps, or a plain vips_cast_* (n == 0)
+struct Route {
+	int from, to;
+	int n;
+	int steps[5];
+	int cast_format; // for the x -> x identity routes
+};
+// the route between two interpretations; nullptr: "no known route"
+const Route *route_find(int from, int to);
+// a route of 3-band steps on the spaces whose sRGB decode does not depend on the tag: what the kernels that fuse
+// a route behind other work (convsep_stream.hip) take as it stands
+bool route_is_plain(const Route &r);
+int step_out_interpretation(int step);
+// (in_format: what enters the step -- the band-replicating steps keep it)
+int step_out_format(int step, int in_format = VIPS_HIP_FORMAT_FLOAT);
+// vips_cast of a whole image (a pointer copy when the format stays)
+int cast_image(_VipsHipImage *in, _VipsHipImage **out, int format);
+// vips_image_guess_interpretation of an image object, as the route table is entered with it.  (Where the guess makes
+// MATRIX or FOURIER of a one-band char or a complex image whose tag cannot be true, the answer here stays MULTIBAND:
+// the reference goes on to convert MATRIX as B_W, colourspace.c:590-593, which this library has no kernels for -- for
+// these images it is "no known route from 'multiband'" as before.)
+static inline int image_guess_interpretation(const _VipsHipImage *im)
+{
+	const int guess = guess_interpretation(im->interpretation, im->width, im->height, im->bands, im->format);
+	return guess != im->interpretation && (guess == 24 || guess == 27) ? VIPS_HIP_INTERPRETATION_MULTIBAND : guess;
+}
 
 } // namespace vh

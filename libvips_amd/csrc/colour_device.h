@@ -1,7 +1,7 @@
-// Device side of the colour routes, shared by colour.hip (the pointwise route kernels) and
-// convsep_stream.hip (the colourspace epilogue fused behind a separable convolution): the
-// per-pixel steps with the reference's intermediate types and operation order, and the chain
-// for one pixel.  Host side: colour.hip.
+// Device side of the colour routes, shared by colour.hip (the pointwise route kernels), colour_sharpen.h (the LabS
+// round trip of the one-kernel sharpen) and convsep_stream.hip (the colourspace epilogue fused behind a separable
+// convolution): the per-pixel steps with the reference's intermediate types and operation order, and the chain
+// for one pixel.  Host side: colour.hip (the route launcher), colour_tables.cpp (the tables).
 #pragma once
 
 #include "colour.h"
@@ -614,8 +614,11 @@ static __device__ __forceinline__ void labs_to_srgb8(const int *Y2v, int L, int 
 	b = (unsigned char) scRGB2sRGB_channel(Y2v, v.c, 255);
 }
 
-// Fill the steps and table pointers of a RouteArgs (tables are built and uploaded on first use);
-// 0 on success.  Defined in colour.hip.
+// colour_tables.cpp: the tables of the calling thread's device (built and uploaded on first use), copied to *out;
+// 0 on success
+int colour_tables(ColourTables *out);
+
+// Fill the steps and table pointers of a RouteArgs; 0 on success.  Defined in colour.hip.
 int colour_route_prepare(const int *steps, int n_steps, RouteArgs *a);
 
 } // namespace vh

@@ -179,6 +179,33 @@ struct DeviceBlock {
 };
 // A second image object on the same pixels (library-owned images only; nullptr otherwise).  It has no orientation.
 _VipsHipImage *image_share(const _VipsHipImage *in);
+// How a one-image entry point starts: bound to the input's device, then the null check
+static inline int enter(const char *domain, _VipsHipImage *in, void *out)
+{
+	if (in && bind_to(in)) // run where the pixels live
+		return -1;
+	if (!in || !out) {
+		error(domain, "null argument");
+		return -1;
+	}
+	return 0;
+}
+// ... and how it ends when it is a generate function over whole images: the output has the input's size and
+// interpretation; gen(in, out) is the region function with its other arguments bound
+template <typename Gen>
+static inline int whole_image(_VipsHipImage *in, _VipsHipImage **out, int bands, int format, Gen gen)
+{
+	ImageRef o(vips_hip_image_new(in->width, in->height, bands, format, in->interpretation));
+	if (!o.im)
+		return -1;
+	VipsHipRegion ri, ro;
+	vips_hip_image_region(in, &ri);
+	vips_hip_image_region(o.im, &ro);
+	if (gen(&ri, &ro))
+		return -1;
+	*out = o.release();
+	return 0;
+}
 // rot.hip: out = in turned and / or mirrored in one launch; op is a sum of ROT_OP_*
 enum { ROT_OP_TRANSPOSE = 1, ROT_OP_FLIPX = 2, ROT_OP_FLIPY = 4 };
 int rot_op_gen(const char *domain, int op, const VipsHipRegion *in, const VipsHipRegion *out);
@@ -499,8 +526,19 @@ int stats_blocks(const _VipsHipImage *in);
 int stats_run(const char *domain, const _VipsHipImage *in, StatsPartial *slab);
 // ops_arith.cpp: the common format of two (arithmetic.c:76-109), for every operation that runs vips__formatalike
 int format_common(int a, int b);
-// ... vips_check_noncomplex's words for a complex format; a pair of windows of the same size, non-complex, not in place
+// header_rules.cpp: the reference's header rules (iofuncs/header.c).  interpretation_bands: the "real" bands a tag
+// implies, 0 for no idea; guess_interpretation: the tag, or the default for the format and the bands where the tag
+// cannot be true of the image (a VipsInterpretation, which may be one vips_hip.h has no name for)
+int interpretation_bands(int interpretation);
+double interpretation_max_alpha(int interpretation);
+int guess_interpretation(int interpretation, int width, int height, int bands, int format);
+double format_max(int format); // -1 for the float formats
+// ... VIPS_CLIP, and one element of vips__vector_to_pels: a constant as an element of `format` (real formats)
+double vips_clip(double lo, double v, double hi);
+void element_to_format(double real, int format, unsigned char *dst);
+// ... vips_check_noncomplex's words for a complex format
 int arithmetic_noncomplex(const char *domain, int format);
+// ops_arith.cpp: a pair of windows of the same size, non-complex, not in place
 int arithmetic_window_pair(const char *domain, const VipsHipRegion *in, const VipsHipRegion *out);
 // logic.hip: the comparisons and booleans of arithmetic/relational.c and boolean.c (ops_logic.cpp checks everything).
 // in2 == nullptr: the right-hand side is the constants (unaryconst.c:90-120).

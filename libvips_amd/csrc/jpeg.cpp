@@ -9,7 +9,7 @@
 //                                   defaults, output cropped to image size / shrink rounded
 //                                   DOWN (libjpeg rounds up and pads), CMYK inverted
 //   vips_thumbnail_build            thumbnail.c:678-1067 on the pre-shrunk image: the
-//                                   thumbnail_image pipeline of ops_colour_conv.cpp
+//                                   thumbnail_image pipeline of ops_thumbnail.cpp
 //
 // The entropy decode is libjpeg's and runs on the host (the same IJG library the reference
 // build links, loaded with dlopen so that libvipship.so itself does not depend on it); the

@@ -33,98 +33,6 @@ struct PlanRef {
 	~PlanRef() { vips_hip_affine_plan_free(p); }
 };
 
-// vips_interpretation_bands, iofuncs/header.c:218-249 (the reference's numbers), for vips_image_hasalpha, image.c:3113
-int interpretation_bands(int interpretation)
-{
-	switch (interpretation) {
-	case 1:  // B_W
-	case 26: // GREY16
-		return 1;
-	case 17: // RGB
-	case 18: // CMC
-	case 19: // LCH
-	case 21: // LABS
-	case 22: // sRGB
-	case 23: // YXY
-	case 12: // XYZ
-	case 13: // LAB
-	case 25: // RGB16
-	case 28: // scRGB
-	case 29: // HSV
-	case 30: // OKLAB
-	case 31: // OKLCH
-		return 3;
-	case 15: // CMYK
-		return 4;
-	default:
-		return 0;
-	}
-}
-
-// vips_interpretation_max_alpha, iofuncs/header.c:194-206
-double interpretation_max_alpha(int interpretation)
-{
-	switch (interpretation) {
-	case VIPS_HIP_INTERPRETATION_GREY16:
-	case VIPS_HIP_INTERPRETATION_RGB16:
-		return 65535.0;
-	case VIPS_HIP_INTERPRETATION_scRGB:
-		return 1.0;
-	default:
-		return 255.0;
-	}
-}
-
-double clip(double lo, double v, double hi)
-{
-	// VIPS_CLIP
-	const double m = hi < v ? hi : v;
-	return lo > m ? lo : m;
-}
-
-// vips__vector_to_pels (conversion/insert.c:244-334) for one element: vips_linear of a black uchar image makes the
-// float, vips_cast (cast.c:123-131, :231-238) clips it as a double and converts
-void element_to_format(double real, int format, unsigned char *dst)
-{
-	const float f = (float) real;
-	const double d = (double) f;
-	switch (format) {
-	case VIPS_HIP_FORMAT_UCHAR: {
-		const unsigned char v = (unsigned char) clip(0, d, UCHAR_MAX);
-		memcpy(dst, &v, sizeof(v));
-		break;
-	}
-	case VIPS_HIP_FORMAT_CHAR: {
-		const signed char v = (signed char) clip(SCHAR_MIN, d, SCHAR_MAX);
-		memcpy(dst, &v, sizeof(v));
-		break;
-	}
-	case VIPS_HIP_FORMAT_USHORT: {
-		const unsigned short v = (unsigned short) clip(0, d, USHRT_MAX);
-		memcpy(dst, &v, sizeof(v));
-		break;
-	}
-	case VIPS_HIP_FORMAT_SHORT: {
-		const short v = (short) clip(SHRT_MIN, d, SHRT_MAX);
-		memcpy(dst, &v, sizeof(v));
-		break;
-	}
-	case VIPS_HIP_FORMAT_UINT: {
-		const unsigned int v = (unsigned int) clip(0, d, UINT_MAX);
-		memcpy(dst, &v, sizeof(v));
-		break;
-	}
-	case VIPS_HIP_FORMAT_INT: {
-		const int v = (int) clip(INT_MIN, d, INT_MAX);
-		memcpy(dst, &v, sizeof(v));
-		break;
-	}
-	default:
-		memcpy(dst, &f, sizeof(f));
-		break;
-	}
-}
-
 void vector_to_ink(const double *background, int n_background, int bands, int format, unsigned char *dst)
 {
 	const int es = format_sizeof(format);

@@ -20,19 +20,6 @@ const char *const NICKNAMES[ARITH_LAST] = { "linear", "invert", "abs", "add", "s
 
 } // namespace
 
-int vh::arithmetic_noncomplex(const char *domain, int format)
-{
-	if (format_iscomplex(format)) {
-		error(domain, "image must be non-complex");
-		return -1;
-	}
-	if (format_sizeof(format) == 0) {
-		error(domain, "unknown band format %d", format);
-		return -1;
-	}
-	return 0;
-}
-
 // arithmetic.c:76-109
 int vh::format_common(int a, int b)
 {
@@ -543,25 +530,13 @@ int vips_hip_abs_gen(const VipsHipRegion *in, const VipsHipRegion *out)
 int vips_hip_linear(VipsHipImage *in, VipsHipImage **out, const VipsHipLinear *args)
 {
 	const char *domain = "linear";
-	if (in && bind_to(in)) // run where the pixels live
+	if (enter(domain, in, out))
 		return -1;
-	if (!in || !out) {
-		error(domain, "null argument");
-		return -1;
-	}
 	int bands, format, single;
 	if (vips_hip_linear_plan(args, in->bands, in->format, &bands, &format, &single, nullptr, nullptr))
 		return -1;
-	ImageRef o(vips_hip_image_new(in->width, in->height, bands, format, in->interpretation));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	if (vips_hip_linear_gen(args, &ri, &ro))
-		return -1;
-	*out = o.release();
-	return 0;
+	return whole_image(in, out, bands, format,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_linear_gen(args, ri, ro); });
 }
 
 int vips_hip_invert(VipsHipImage *in, VipsHipImage **out)

@@ -12,89 +12,12 @@ using namespace vh;
 
 namespace {
 
-// vips_interpretation_max_alpha, iofuncs/header.c:194-206
-double interpretation_max_alpha(int interpretation)
-{
-	switch (interpretation) {
-	case VIPS_HIP_INTERPRETATION_GREY16:
-	case VIPS_HIP_INTERPRETATION_RGB16:
-		return 65535.0;
-	case VIPS_HIP_INTERPRETATION_scRGB:
-		return 1.0;
-	default:
-		return 255.0;
-	}
-}
-
-// vips_image_get_format_max, iofuncs/header.c
-double format_max(int format)
-{
-	switch (format) {
-	case VIPS_HIP_FORMAT_UCHAR: return UCHAR_MAX;
-	case VIPS_HIP_FORMAT_CHAR: return SCHAR_MAX;
-	case VIPS_HIP_FORMAT_USHORT: return USHRT_MAX;
-	case VIPS_HIP_FORMAT_SHORT: return SHRT_MAX;
-	case VIPS_HIP_FORMAT_UINT: return UINT_MAX;
-	case VIPS_HIP_FORMAT_INT: return INT_MAX;
-	default: return -1;
-	}
-}
-
-double clip(double lo, double v, double hi)
-{
-	// VIPS_CLIP
-	const double m = hi < v ? hi : v;
-	return lo > m ? lo : m;
-}
-
-// vips__vector_to_pels (insert.c:244-334) for one element: vips_linear of a black uchar image makes the float,
-// vips_cast (cast.c) clips it as a double and converts
-void element_to_format(double real, int format, unsigned char *dst)
-{
-	const float f = (float) real;
-	const double d = (double) f;
-	switch (format) {
-#define INT_CASE(F, T, LO, HI) \
-	case F: { \
-		const T v = (T) clip(LO, d, HI); \
-		memcpy(dst, &v, sizeof(v)); \
-		break; \
-	}
-		INT_CASE(VIPS_HIP_FORMAT_UCHAR, unsigned char, 0, UCHAR_MAX)
-		INT_CASE(VIPS_HIP_FORMAT_CHAR, signed char, SCHAR_MIN, SCHAR_MAX)
-		INT_CASE(VIPS_HIP_FORMAT_USHORT, unsigned short, 0, USHRT_MAX)
-		INT_CASE(VIPS_HIP_FORMAT_SHORT, short, SHRT_MIN, SHRT_MAX)
-		INT_CASE(VIPS_HIP_FORMAT_UINT, unsigned int, 0, UINT_MAX)
-		INT_CASE(VIPS_HIP_FORMAT_INT, int, INT_MIN, INT_MAX)
-#undef INT_CASE
-	case VIPS_HIP_FORMAT_DOUBLE:
-		memcpy(dst, &d, sizeof(d));
-		break;
-	default:
-		memcpy(dst, &f, sizeof(f));
-		break;
-	}
-}
-
 // the class default of every `background` here: one zero
 void background_of(int n, const double *given, int *n_out, const double **out)
 {
 	static const double zero[1] = { 0.0 };
 	*n_out = n > 0 ? n : 1;
 	*out = n > 0 ? given : zero;
-}
-
-int check_noncomplex(const char *domain, int format)
-{
-	if (format_iscomplex(format)) {
-		error(domain, "image must be non-complex");
-		return -1;
-	}
-	if (format_sizeof(format) == 0) {
-		error(domain, "unknown band format %d", format);
-		return -1;
-	}
-	return 0;
 }
 
 // one axis of vips_hip_embed_need: canvas columns [left, left + n) of an image of `size` at `pos` -> [*lo, *hi] of it,
@@ -216,7 +139,7 @@ int insert_image(const char *domain, VipsHipImage *main, VipsHipImage *sub, Vips
 		error(domain, "images must have the same number of bands, or one must be single-band");
 		return -1;
 	}
-	if (check_noncomplex(domain, main->format) || check_noncomplex(domain, sub->format))
+	if (arithmetic_noncomplex(domain, main->format) || arithmetic_noncomplex(domain, sub->format))
 		return -1;
 	if (x < -INSERT_COORD_MAX || x > INSERT_COORD_MAX || y < -INSERT_COORD_MAX || y > INSERT_COORD_MAX) {
 		error(domain, "position out of range");
@@ -376,7 +299,7 @@ int vips_hip_embed_plan(const char *nickname, const VipsHipEmbed *args, int in_w
 		error(domain, "bad arguments");
 		return -1;
 	}
-	if (check_noncomplex(domain, format))
+	if (arithmetic_noncomplex(domain, format))
 		return -1;
 	if (width < 1 || width > COORD_MAX || height < 1 || height > COORD_MAX || x < -COORD_MAX || x > COORD_MAX || y < -COORD_MAX ||
 		y > COORD_MAX) {
@@ -501,7 +424,7 @@ int vips_hip_embed_gen(int extend, const void *ink, int x, int y, const VipsHipR
 	}
 	if (check_region(domain, in) || check_region(domain, out))
 		return -1;
-	if (check_noncomplex(domain, in->format))
+	if (arithmetic_noncomplex(domain, in->format))
 		return -1;
 	if (in->bands != out->bands || in->format != out->format) {
 		error(domain, "input and output must have the same bands and format");
@@ -571,7 +494,7 @@ int vips_hip_flatten_gen(const VipsHipRegion *in, const VipsHipRegion *out, doub
 	}
 	if (check_region(domain, in) || check_region(domain, out))
 		return -1;
-	if (check_noncomplex(domain, in->format))
+	if (arithmetic_noncomplex(domain, in->format))
 		return -1;
 	if (in->bands < 2 || out->bands != in->bands - 1 || in->format != out->format) {
 		error(domain, "the output must have the input's format and one band less");
@@ -652,7 +575,7 @@ int vips_hip_flatten(VipsHipImage *in, VipsHipImage **out, const VipsHipFlatten 
 	}
 	if (in->bands == 1) // "Trivial case: fall back to copy()."
 		return vips_hip_cast(in, out, in->format);
-	if (check_noncomplex(domain, in->format))
+	if (arithmetic_noncomplex(domain, in->format))
 		return -1;
 	const double max_alpha = args->max_alpha_set ? args->max_alpha : interpretation_max_alpha(in->interpretation);
 	// :457-470: integer images whose max_alpha is below the format's range go through double
@@ -711,7 +634,7 @@ int vips_hip_addalpha(VipsHipImage *in, VipsHipImage **out)
 		error(domain, "null argument");
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format))
+	if (arithmetic_noncomplex(domain, in->format))
 		return -1;
 	const double max_alpha = interpretation_max_alpha(in->interpretation);
 	unsigned long long alpha = 0;

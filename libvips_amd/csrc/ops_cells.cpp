@@ -15,19 +15,6 @@ namespace {
 
 const int ARG_MAX_COORD = 1000000; // the range of across, down, shim, hspacing and vspacing (arrayjoin.c, replicate.c, grid.c)
 
-int check_noncomplex(const char *domain, int format)
-{
-	if (format_iscomplex(format)) {
-		error(domain, "image must be non-complex");
-		return -1;
-	}
-	if (format_sizeof(format) == 0) {
-		error(domain, "unknown band format %d", format);
-		return -1;
-	}
-	return 0;
-}
-
 int check_pel(const char *domain, int bands, int format)
 {
 	if ((long long) bands * format_sizeof(format) > CANVAS_MAX_PEL) {
@@ -55,7 +42,7 @@ int check_pair(const char *domain, const VipsHipRegion *in, const VipsHipRegion 
 		error(domain, "null argument");
 		return -1;
 	}
-	if (check_region(domain, in) || check_region(domain, out) || check_noncomplex(domain, in->format))
+	if (check_region(domain, in) || check_region(domain, out) || arithmetic_noncomplex(domain, in->format))
 		return -1;
 	if (in->bands != out->bands || in->format != out->format) {
 		error(domain, "input and output must have the same bands and format");
@@ -261,7 +248,7 @@ int vips_hip_arrayjoin(VipsHipImage **in, int n, VipsHipImage **out, const VipsH
 			error(domain, "the images are on different devices");
 			return -1;
 		}
-		if (check_noncomplex(domain, in[i]->format))
+		if (arithmetic_noncomplex(domain, in[i]->format))
 			return -1;
 	}
 	static const double zero[1] = { 0.0 };
@@ -460,7 +447,7 @@ int vips_hip_replicate(VipsHipImage *in, VipsHipImage **out, int across, int dow
 		error(domain, "across and down must be 1 .. %d", ARG_MAX_COORD);
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format) || check_pel(domain, in->bands, in->format))
+	if (arithmetic_noncomplex(domain, in->format) || check_pel(domain, in->bands, in->format))
 		return -1;
 	return whole_image(in, out, (long long) in->width * across, (long long) in->height * down, domain,
 		[](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_replicate_gen(0, 0, ri, ro); });
@@ -475,7 +462,7 @@ int vips_hip_wrap(VipsHipImage *in, VipsHipImage **out, int x, int y, int x_set,
 		error(domain, "null argument");
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format) || check_pel(domain, in->bands, in->format))
+	if (arithmetic_noncomplex(domain, in->format) || check_pel(domain, in->bands, in->format))
 		return -1;
 	// wrap.c:78-91; INT_MIN has no negative
 	if (x == INT_MIN || y == INT_MIN) {
@@ -505,7 +492,7 @@ int vips_hip_grid(VipsHipImage *in, VipsHipImage **out, int tile_height, int acr
 		error(domain, "tile_height, across and down must be 1 .. 10000000");
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format) || check_pel(domain, in->bands, in->format))
+	if (arithmetic_noncomplex(domain, in->format) || check_pel(domain, in->bands, in->format))
 		return -1;
 	// grid.c:162-167
 	if (in->height % tile_height != 0 || in->height / tile_height != (long long) across * down) {
@@ -529,7 +516,7 @@ int vips_hip_zoom(VipsHipImage *in, VipsHipImage **out, int xfac, int yfac)
 		error(domain, "zoom factors should be >= 1");
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format))
+	if (arithmetic_noncomplex(domain, in->format))
 		return -1;
 	// zoom.c:322-329
 	if ((double) in->width * xfac > (double) INT_MAX / 2 || (double) in->height * yfac > (double) INT_MAX / 2) {
@@ -555,7 +542,7 @@ int vips_hip_subsample(VipsHipImage *in, VipsHipImage **out, int xfac, int yfac)
 		error(domain, "factors should be positive");
 		return -1;
 	}
-	if (check_noncomplex(domain, in->format))
+	if (arithmetic_noncomplex(domain, in->format))
 		return -1;
 	if (xfac == 1 && yfac == 1) // subsample.c:207-209: vips_image_write
 		return vips_hip_cast(in, out, in->format);

@@ -198,23 +198,11 @@ int vips_hip_edge_step(int what)
 static int edge_image(VipsHipImage *in, VipsHipImage **out, int edge)
 {
 	const char *domain = edge_names[edge];
-	if (in && bind_to(in)) // run where the pixels live
+	if (enter(domain, in, out))
 		return -1;
-	if (!in || !out) {
-		error(domain, "null argument");
-		return -1;
-	}
 	// both paths end in uchar: vips_edge_uchar_gen writes the conv's format, the float path vips_cast_uchar (edge.c:174)
-	ImageRef o(vips_hip_image_new(in->width, in->height, in->bands, VIPS_HIP_FORMAT_UCHAR, in->interpretation));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	if (vips_hip_edge_gen(&ri, &ro, edge))
-		return -1;
-	*out = o.release();
-	return 0;
+	return whole_image(in, out, in->bands, VIPS_HIP_FORMAT_UCHAR,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_edge_gen(ri, ro, edge); });
 }
 
 int vips_hip_sobel(VipsHipImage *in, VipsHipImage **out)

@@ -18,73 +18,6 @@ const char *format_name(int format)
 	return format >= 0 && format <= 9 ? names[format] : "unknown";
 }
 
-// vips_interpretation_bands, iofuncs/header.c:218-249, for the interpretations this library names
-int interpretation_bands(int type)
-{
-	switch (type) {
-	case VIPS_HIP_INTERPRETATION_B_W:
-	case VIPS_HIP_INTERPRETATION_GREY16:
-		return 1;
-	case VIPS_HIP_INTERPRETATION_XYZ:
-	case VIPS_HIP_INTERPRETATION_LAB:
-	case VIPS_HIP_INTERPRETATION_LABS:
-	case VIPS_HIP_INTERPRETATION_sRGB:
-	case VIPS_HIP_INTERPRETATION_RGB16:
-	case VIPS_HIP_INTERPRETATION_scRGB:
-		return 3;
-	default:
-		return 0;
-	}
-}
-
-// vips_image_guess_interpretation, iofuncs/header.c:589-759, for uncoded images: the tag, unless it cannot be true of
-// such an image -- then the default for the format and the bands
-int guess_interpretation(int type, int width, int height, int bands, int format)
-{
-	bool sane = bands >= interpretation_bands(type);
-	const bool is8 = format == VIPS_HIP_FORMAT_UCHAR || format == VIPS_HIP_FORMAT_CHAR;
-	const bool isuint = format == VIPS_HIP_FORMAT_UCHAR || format == VIPS_HIP_FORMAT_USHORT || format == VIPS_HIP_FORMAT_UINT;
-	switch (type) {
-	case VIPS_HIP_INTERPRETATION_MULTIBAND:
-		sane = false;
-		break;
-	case VIPS_HIP_INTERPRETATION_HISTOGRAM:
-		if (width > 1 && height > 1)
-			sane = false;
-		break;
-	case VIPS_HIP_INTERPRETATION_scRGB:
-		if (format != VIPS_HIP_FORMAT_FLOAT && format != VIPS_HIP_FORMAT_DOUBLE)
-			sane = false;
-		break;
-	case VIPS_HIP_INTERPRETATION_LABS:
-		if (isuint || is8)
-			sane = false;
-		break;
-	case VIPS_HIP_INTERPRETATION_RGB16:
-	case VIPS_HIP_INTERPRETATION_GREY16:
-		if (is8)
-			sane = false;
-		break;
-	default:
-		break;
-	}
-	if (sane)
-		return type;
-	switch (format) {
-	case VIPS_HIP_FORMAT_UCHAR:
-	case VIPS_HIP_FORMAT_SHORT:
-	case VIPS_HIP_FORMAT_UINT:
-	case VIPS_HIP_FORMAT_INT:
-	case VIPS_HIP_FORMAT_FLOAT:
-	case VIPS_HIP_FORMAT_DOUBLE:
-		return bands <= 2 ? VIPS_HIP_INTERPRETATION_B_W : bands <= 4 ? VIPS_HIP_INTERPRETATION_sRGB : VIPS_HIP_INTERPRETATION_MULTIBAND;
-	case VIPS_HIP_FORMAT_USHORT:
-		return bands <= 2 ? VIPS_HIP_INTERPRETATION_GREY16 : bands <= 4 ? VIPS_HIP_INTERPRETATION_RGB16 : VIPS_HIP_INTERPRETATION_MULTIBAND;
-	default: // char: MATRIX for one band, which this library has no name for
-		return VIPS_HIP_INTERPRETATION_MULTIBAND;
-	}
-}
-
 // one element of a table: (TYPE) v as the reference's PACK_TABLE stores the identity, maplut.c:562-581
 void put_identity(unsigned char *q, int format, int x)
 {
@@ -418,22 +351,10 @@ int vips_hip_hist_local_step(int what)
 
 int vips_hip_hist_local(VipsHipImage *in, VipsHipImage **out, int width, int height, int max_slope)
 {
-	if (in && bind_to(in)) // run where the pixels live
+	if (enter("hist_local", in, out))
 		return -1;
-	if (!in || !out) {
-		error("hist_local", "null argument");
-		return -1;
-	}
-	ImageRef o(vips_hip_image_new(in->width, in->height, in->bands, VIPS_HIP_FORMAT_UCHAR, in->interpretation));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	if (vips_hip_hist_local_gen(&ri, &ro, width, height, max_slope))
-		return -1;
-	*out = o.release();
-	return 0;
+	return whole_image(in, out, in->bands, VIPS_HIP_FORMAT_UCHAR,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_hist_local_gen(ri, ro, width, height, max_slope); });
 }
 
 // vips_stdif_generate, stdif.c:135-253, with the checks of vips_stdif_build :273-280
@@ -466,22 +387,10 @@ int vips_hip_stdif_step(int what)
 
 int vips_hip_stdif(VipsHipImage *in, VipsHipImage **out, int width, int height, double a, double m0, double b, double s0)
 {
-	if (in && bind_to(in)) // run where the pixels live
+	if (enter("stdif", in, out))
 		return -1;
-	if (!in || !out) {
-		error("stdif", "null argument");
-		return -1;
-	}
-	ImageRef o(vips_hip_image_new(in->width, in->height, in->bands, VIPS_HIP_FORMAT_UCHAR, in->interpretation));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	if (vips_hip_stdif_gen(&ri, &ro, width, height, a, m0, b, s0))
-		return -1;
-	*out = o.release();
-	return 0;
+	return whole_image(in, out, in->bands, VIPS_HIP_FORMAT_UCHAR,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_stdif_gen(ri, ro, width, height, a, m0, b, s0); });
 }
 
 } // extern "C"

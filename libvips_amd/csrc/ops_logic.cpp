@@ -70,40 +70,6 @@ int bandalike(const char *domain, const int *bands, const int *interpretations, 
 	return 0;
 }
 
-// the output of a one-image operation: the input's size and interpretation
-VipsHipImage *output_like(const VipsHipImage *in, int bands, int format)
-{
-	return vips_hip_image_new(in->width, in->height, bands, format, in->interpretation);
-}
-
-typedef int (*GenFn)(const void *closure, const VipsHipRegion *in, const VipsHipRegion *out);
-
-// whole images through a generate function
-int whole_image(VipsHipImage *in, VipsHipImage **out, int bands, int format, GenFn fn, const void *closure)
-{
-	ImageRef o(output_like(in, bands, format));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	if (fn(closure, &ri, &ro))
-		return -1;
-	*out = o.release();
-	return 0;
-}
-
-int enter(const char *domain, VipsHipImage *in, void *out)
-{
-	if (in && bind_to(in)) // run where the pixels live
-		return -1;
-	if (!in || !out) {
-		error(domain, "null argument");
-		return -1;
-	}
-	return 0;
-}
-
 struct ConstCall {
 	int family, op;
 	const double *c;
@@ -147,11 +113,6 @@ int const_gen(const ConstCall &call, const VipsHipRegion *in, const VipsHipRegio
 	return logic_run(domain, call.family, call.op, in->format, a);
 }
 
-int const_gen_fn(const void *closure, const VipsHipRegion *in, const VipsHipRegion *out)
-{
-	return const_gen(*(const ConstCall *) closure, in, out);
-}
-
 int const_image(int family, VipsHipImage *in, VipsHipImage **out, int op, const double *c, int n)
 {
 	const char *domain = CONST_NICKNAMES[family];
@@ -164,7 +125,8 @@ int const_image(int family, VipsHipImage *in, VipsHipImage **out, int op, const 
 	if (vips_hip_const_plan(domain, c, n, in->bands, in->format, &bands, nullptr, nullptr, nullptr))
 		return -1;
 	const ConstCall call = { family, op, c, n };
-	return whole_image(in, out, bands, vips_hip_logic_format(family, in->format), const_gen_fn, &call);
+	return whole_image(in, out, bands, vips_hip_logic_format(family, in->format),
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return const_gen(call, ri, ro); });
 }
 
 // closure: the family and the operation, which is checked here: behind the device check, before the plan
@@ -221,33 +183,6 @@ void band_output(const VipsHipRegion *out, BandArgs *a)
 	a->elems = out->width * out->bands;
 	a->height = out->height;
 	a->out_bands = out->bands;
-}
-
-struct BandCall {
-	int op, band;
-	const double *c;
-	int n;
-};
-
-int bandmean_gen_fn(const void *, const VipsHipRegion *in, const VipsHipRegion *out)
-{
-	return vips_hip_bandmean_gen(in, out);
-}
-
-int bandbool_gen_fn(const void *closure, const VipsHipRegion *in, const VipsHipRegion *out)
-{
-	return vips_hip_bandbool_gen(((const BandCall *) closure)->op, in, out);
-}
-
-int extract_band_gen_fn(const void *closure, const VipsHipRegion *in, const VipsHipRegion *out)
-{
-	return vips_hip_extract_band_gen(((const BandCall *) closure)->band, in, out);
-}
-
-int bandjoin_const_gen_fn(const void *closure, const VipsHipRegion *in, const VipsHipRegion *out)
-{
-	const BandCall *call = (const BandCall *) closure;
-	return vips_hip_bandjoin_const_gen(call->c, call->n, in, out);
 }
 
 int check_bandbool(int op)
@@ -626,8 +561,8 @@ int vips_hip_bandjoin_const(VipsHipImage *in, VipsHipImage **out, const double *
 		error(domain, "1 to %d constants", BAND_MAX_SOURCES - 1);
 		return -1;
 	}
-	const BandCall call = { 0, 0, c, n };
-	return whole_image(in, out, in->bands + n, in->format, bandjoin_const_gen_fn, &call);
+	return whole_image(in, out, in->bands + n, in->format,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_bandjoin_const_gen(c, n, ri, ro); });
 }
 
 int vips_hip_extract_band_gen(int band, const VipsHipRegion *in, const VipsHipRegion *out)
@@ -658,8 +593,8 @@ int vips_hip_extract_band(VipsHipImage *in, VipsHipImage **out, int band, int n)
 	// extract.c:408-410
 	if (band == 0 && n == in->bands)
 		return vips_hip_cast(in, out, in->format);
-	const BandCall call = { 0, band, nullptr, 0 };
-	return whole_image(in, out, n, in->format, extract_band_gen_fn, &call);
+	return whole_image(in, out, n, in->format,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_extract_band_gen(band, ri, ro); });
 }
 
 int vips_hip_bandmean_gen(const VipsHipRegion *in, const VipsHipRegion *out)
@@ -686,7 +621,7 @@ int vips_hip_bandmean(VipsHipImage *in, VipsHipImage **out)
 	// bandmean.c:162-164
 	if (in->bands == 1)
 		return vips_hip_cast(in, out, in->format);
-	return whole_image(in, out, 1, in->format, bandmean_gen_fn, nullptr);
+	return whole_image(in, out, 1, in->format, vips_hip_bandmean_gen);
 }
 
 int vips_hip_bandbool_gen(int boolean, const VipsHipRegion *in, const VipsHipRegion *out)
@@ -716,8 +651,8 @@ int vips_hip_bandbool(VipsHipImage *in, VipsHipImage **out, int boolean)
 	// bandbool.c:89-90: one band is a copy (of the image as it is: a float image stays float)
 	if (in->bands == 1)
 		return vips_hip_cast(in, out, in->format);
-	const BandCall call = { boolean, 0, nullptr, 0 };
-	return whole_image(in, out, 1, vips_hip_logic_format(1, in->format), bandbool_gen_fn, &call);
+	return whole_image(in, out, 1, vips_hip_logic_format(1, in->format),
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_bandbool_gen(boolean, ri, ro); });
 }
 
 int vips_hip_logic_step(int what)

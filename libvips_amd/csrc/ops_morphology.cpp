@@ -188,22 +188,10 @@ int vips_hip_rank_step(int what)
 // vips_rank_build, rank.c:458-539
 int vips_hip_rank(VipsHipImage *in, VipsHipImage **out, int width, int height, int index)
 {
-	if (in && bind_to(in)) // run where the pixels live
+	if (enter("rank", in, out))
 		return -1;
-	if (!in || !out) {
-		error("rank", "null argument");
-		return -1;
-	}
-	ImageRef o(vips_hip_image_new(in->width, in->height, in->bands, in->format, in->interpretation));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	if (vips_hip_rank_gen(&ri, &ro, width, height, index))
-		return -1;
-	*out = o.release();
-	return 0;
+	return whole_image(in, out, in->bands, in->format,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_rank_gen(ri, ro, width, height, index); });
 }
 
 // vips_median, rank.c:639-671
@@ -219,22 +207,10 @@ int vips_hip_median(VipsHipImage *in, VipsHipImage **out, int size)
 // vips_morph_build, morph.c:828-941
 int vips_hip_morph(VipsHipImage *in, VipsHipImage **out, const double *mask, int mask_width, int mask_height, int morph)
 {
-	if (in && bind_to(in)) // run where the pixels live
+	if (enter("morph", in, out))
 		return -1;
-	if (!in || !out) {
-		error("morph", "null argument");
-		return -1;
-	}
-	ImageRef o(vips_hip_image_new(in->width, in->height, in->bands, VIPS_HIP_FORMAT_UCHAR, in->interpretation));
-	if (!o.im)
-		return -1;
-	VipsHipRegion ri, ro;
-	vips_hip_image_region(in, &ri);
-	vips_hip_image_region(o.im, &ro);
-	if (vips_hip_morph_gen(&ri, &ro, mask, mask_width, mask_height, morph))
-		return -1;
-	*out = o.release();
-	return 0;
+	return whole_image(in, out, in->bands, VIPS_HIP_FORMAT_UCHAR,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_morph_gen(ri, ro, mask, mask_width, mask_height, morph); });
 }
 
 } // extern "C"

@@ -34,34 +34,6 @@ int outputs(const VipsHipImage *in, int format, ImageRef *columns, ImageRef *row
 	return columns->im && rows->im ? 0 : -1;
 }
 
-// vips_interpretation_bands, iofuncs/header.c:218-249 (the reference's numbers), for vips_image_hasalpha, image.c:3113
-int interpretation_bands(int interpretation)
-{
-	switch (interpretation) {
-	case 1:  // B_W
-	case 26: // GREY16
-		return 1;
-	case 17: // RGB
-	case 18: // CMC
-	case 19: // LCH
-	case 21: // LABS
-	case 22: // sRGB
-	case 23: // YXY
-	case 12: // XYZ
-	case 13: // LAB
-	case 25: // RGB16
-	case 28: // scRGB
-	case 29: // HSV
-	case 30: // OKLAB
-	case 31: // OKLCH
-		return 3;
-	case 15: // CMYK
-		return 4;
-	default:
-		return 0;
-	}
-}
-
 bool hasalpha(const VipsHipImage *im)
 {
 	const int bands = interpretation_bands(im->interpretation);

@@ -23,7 +23,7 @@ static int rsh_launch(int vs, const RshArgs &a, const RshPtrs &p, unsigned int b
 namespace {
 
 // the per-device tables of the kernel, made once from the reference's own table code
-// (colour.hip: calcul_tables = LabQ2sRGB.c:130-160, table_init = XYZ2Lab.c:92-106)
+// (colour_tables.cpp: calcul_tables = LabQ2sRGB.c:130-160, table_init = XYZ2Lab.c:92-106)
 struct RshTables {
 	float *v2Y = nullptr;
 	RshPair *Y2v = nullptr;
