@@ -1557,6 +1557,35 @@ VIPS_HIP_API int vips_hip_find_trim(VipsHipImage *in, const VipsHipFindTrim *arg
  * block's waves -- for tests that want sizes round them. */
 VIPS_HIP_API int vips_hip_trim_step(int what);
 
+/* ------------------------------------------------ regions: labelregions, countlines
+ *
+ * vips_labelregions (morphology/labelregions.c) and vips_countlines (countlines.c) on images in HBM (regions.hip),
+ * identical to the reference in values, format, bands, size and interpretation.
+ */
+
+/* vips_labelregions_build (labelregions.c:60-109).  @mask: one band of int, the input's size, interpretation multiband
+ * (vips_black cast to int, :76-78): every pel holds the number of its region.  Regions are the 4-connected components
+ * of pels that are BYTEWISE equal over the whole pel (draw_flood.c:223-235: +0.0 and -0.0 are two regions, two NaNs with
+ * one payload are one), numbered from 1 in raster order of each region's first pel.  *@segments (may be NULL) is the
+ * number of regions PLUS ONE: the reference's counter starts at 1 and is stored after the last increment (:86-106).
+ * Any real format, pels of up to 32 bytes; complex images, wider pels and images of 2^31 pels and more (a label is an
+ * int) are refused by name.  Six launches -- a union-find whose root is a region's smallest linear index, so the
+ * numbering is the reference's whatever order the device runs in, the same bits on every run -- and ONE int to the
+ * host, when @segments is given.  The planes (an int a pel and 5 / 64 of a byte) come from the pool; there are no
+ * strips, since a region can span the image: what does not fit the device's memory is refused with the sizes. */
+VIPS_HIP_API int vips_hip_labelregions(VipsHipImage *in, VipsHipImage **mask, int *segments);
+/* 0 / 1: the width / height in pels of the tile a block of label_tiles owns; 2: the largest pel in bytes -- for tests
+ * that want sizes round them. */
+VIPS_HIP_API int vips_hip_labelregions_step(int what);
+/* vips_countlines_build (countlines.c:74-121): the reference's chain (moreeq_const 128, a two-tap integer conv with
+ * (-1, 1) clipped to uchar, project, avg, / 255) counts RISES -- an element below 128 followed by one at or above 128,
+ * down its column for @direction 0 (horizontal), along its row for 1 (vertical); falls do not count and the copied edge
+ * makes no transition -- and divides by the extent across the direction times the bands.  The comparison is
+ * vips_hip_relational_const's for each format.  ONE read-only launch, ONE 64-bit count to the host, and the reference's
+ * divisions in its order on the host.  Any real format and any number of bands; complex images are refused by name, and
+ * so are images of more than 2^25 pels along the count (the reference's uint sums could wrap there). */
+VIPS_HIP_API int vips_hip_countlines(VipsHipImage *in, int direction, double *nolines);
+
 #ifdef __cplusplus
 }
 #endif

@@ -526,6 +526,10 @@ _SIGNATURES = {
     "vips_hip_find_trim_table": (c_int, [P(FindTrim), c_int, c_int, P(c_int), P(ctypes.c_ubyte)]),
     "vips_hip_find_trim": (c_int, [c_void_p, P(FindTrim)] + [P(c_int)] * 4),
     "vips_hip_trim_step": (c_int, [c_int]),
+    # labelregions / countlines
+    "vips_hip_labelregions": (c_int, [c_void_p, P(c_void_p), P(c_int)]),
+    "vips_hip_labelregions_step": (c_int, [c_int]),
+    "vips_hip_countlines": (c_int, [c_void_p, c_int, P(c_double)]),
 }
 
 MISSING = []

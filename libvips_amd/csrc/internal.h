@@ -608,4 +608,22 @@ int trim_fused_run(const char *domain, const _VipsHipImage *in, int median, cons
 // blocks a project / profile launch has once more than one row of blocks is needed, 4 the elements of a fused tile's row,
 // 5 the rows a fused block takes, 6 the rows between two meetings of a project / profile block's waves
 int trim_tile(int what);
+// regions.hip: vips_labelregions of a checked image (ops_regions.cpp checks everything) in six launches.  `planes` is
+// device memory of regions_layout()'s `bytes`: the parent plane (width * height ints), the seams' bits, the chunk counts
+// and the total, at the offsets the layout gives; all of it is rewritten by every call.  `out` is the mask, width *
+// height ints.  After the run the int at planes + layout.total holds the number of regions.
+constexpr int REGIONS_MAX_PEL = 32; // bytes
+struct RegionsLayout {
+	size_t parent, vseam, hseam, counts, total; // offsets into the planes, bytes
+	size_t bytes;
+	long long n_vseam, n_hseam; // seam bytes: (tiles across - 1) * height, (tiles down - 1) * width
+	int chunks;
+};
+void regions_layout(int width, int height, RegionsLayout *l);
+int regions_label_run(const char *domain, const _VipsHipImage *in, unsigned char *planes, int *out);
+// ... vips_countlines' count in ONE read-only launch: the rises (an element below 128 followed by one at or above it,
+// down the columns, or along the rows for `vertical`) of every band are ADDED to *rises, device memory, zero before
+int countlines_run(const char *domain, const _VipsHipImage *in, int vertical, unsigned long long *rises);
+// regions_tile: 0 / 1 the pels / rows of a tile of label_tiles, 2 the largest pel in bytes, 3 the linear indices of a chunk
+int regions_tile(int what);
 } // namespace vh

@@ -794,6 +794,25 @@ class Image(object):
                                      *[ctypes.byref(v) for v in box]))
         return tuple(v.value for v in box)
 
+    # libvips/morphology: vips_labelregions / vips_countlines
+    def labelregions(self, with_options=False):
+        """vips_labelregions: a one-band int mask that numbers the 4-connected regions of bytewise equal pels from 1, in
+        raster order of each region's first pel.  ``with_options``: also return ``{"segments"}``, the number of regions
+        plus one, as the reference counts."""
+        out, segments = ctypes.c_void_p(), ctypes.c_int()
+        check(lib.vips_hip_labelregions(self._h, ctypes.byref(out), ctypes.byref(segments) if with_options else None))
+        mask = Image(out.value)
+        if with_options:
+            return mask, {"segments": segments.value}
+        return mask
+
+    def countlines(self, direction):
+        """vips_countlines: the mean number of rises (below 128, then at or above it) down the columns
+        (``"horizontal"`` lines) or along the rows (``"vertical"``)."""
+        out = ctypes.c_double()
+        check(lib.vips_hip_countlines(self._h, _enum(DIRECTIONS, direction, "direction"), ctypes.byref(out)))
+        return out.value
+
     # the operators, as pyvips spells them: an image on the other side is the two-image operation, a number or a list
     # of numbers vips_linear.  There is no __rtruediv__: pyvips makes `2 / image` of vips_math2 (pow), which is not on
     # the device, so that spelling raises TypeError rather than leave it
