@@ -2781,6 +2781,219 @@ vips_abs_hip_init(VipsAbsHip *abs)
 {
 }
 
+/* round_hip / sign_hip / clamp_hip / remainder_const_hip: arithmetic/round.c:181-190, sign.c:167-179, clamp.c:144-174,
+ * remainder.c:360-380.  Pointwise strip classes on the region forms, with the originals' arguments; the output's header
+ * is the original's (a one-band image against n constants makes n bands).  Complex images, and more constants than the
+ * kernels keep, are the original's (hip_wants_original). */
+typedef struct _VipsArith2Hip {
+	VipsHipOp parent_instance;
+	VipsOperationRound round;
+	double min, max;
+	VipsArrayDouble *c;
+} VipsArith2Hip;
+
+typedef VipsArith2Hip VipsRoundHip;
+typedef VipsArith2Hip VipsSignHip;
+typedef VipsArith2Hip VipsClampHip;
+typedef VipsArith2Hip VipsRemainderConstHip;
+
+static const double *
+arith2_hip_constants(VipsHipOp *op, int *n)
+{
+	VipsArith2Hip *arith = (VipsArith2Hip *) op;
+
+	*n = 0;
+	return arith->c ? vips_array_double_get(arith->c, n) : NULL;
+}
+
+static int
+vips_round_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_round(in, out, ((VipsArith2Hip *) op)->round);
+}
+
+static int
+vips_sign_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_sign(in, out);
+}
+
+static int
+vips_clamp_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	return vips_hip_clamp(in, out, ((VipsArith2Hip *) op)->min, ((VipsArith2Hip *) op)->max);
+}
+
+static int
+vips_remainder_const_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	int n;
+	const double *c = arith2_hip_constants(op, &n);
+
+	return vips_hip_remainder_const(in, out, c, n);
+}
+
+/* (no plan: the region forms take the operation's own arguments) */
+static int
+vips_round_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_round_gen(((VipsArith2Hip *) op)->round, in, out);
+}
+
+static int
+vips_sign_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_sign_gen(in, out);
+}
+
+static int
+vips_clamp_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	return vips_hip_clamp_gen(((VipsArith2Hip *) op)->min, ((VipsArith2Hip *) op)->max, in, out);
+}
+
+static int
+vips_remainder_const_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	int n;
+	const double *c = arith2_hip_constants(op, &n);
+
+	return vips_hip_remainder_const_gen(c, n, in, out);
+}
+
+#define ARITH2_HIP_STRIPS(type_name) \
+	class->strip_open = vips_invert_hip_strip_open; \
+	class->strip_need = vips_linear_hip_strip_need; \
+	class->strip_run = type_name##_strip_run; \
+	class->strip_close = vips_invert_hip_strip_close;
+
+HIP_SUBCLASS_FULL(VipsRoundHip, vips_round_hip, "round_hip", "perform a round function on an image (MI355X)",
+	ARITH2_HIP_STRIPS(vips_round_hip))
+HIP_SUBCLASS_FULL(VipsSignHip, vips_sign_hip, "sign_hip", "unit vector of pixel (MI355X)", ARITH2_HIP_STRIPS(vips_sign_hip))
+HIP_SUBCLASS_FULL(VipsClampHip, vips_clamp_hip, "clamp_hip", "clamp values of an image (MI355X)", ARITH2_HIP_STRIPS(vips_clamp_hip))
+HIP_SUBCLASS_FULL(VipsRemainderConstHip, vips_remainder_const_hip, "remainder_const_hip",
+	"remainder after integer division of an image and a constant (MI355X)", ARITH2_HIP_STRIPS(vips_remainder_const_hip))
+
+static void
+vips_round_hip_args(VipsRoundHipClass *class)
+{
+	VIPS_ARG_ENUM(class, "round", 200, "Round operation", "Rounding operation to perform",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsArith2Hip, round),
+		VIPS_TYPE_OPERATION_ROUND, VIPS_OPERATION_ROUND_RINT);
+}
+
+static void
+vips_sign_hip_args(VipsSignHipClass *class)
+{
+}
+
+static void
+vips_clamp_hip_args(VipsClampHipClass *class)
+{
+	VIPS_ARG_DOUBLE(class, "min", 10, "Min", "Minimum value",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsArith2Hip, min), -INFINITY, INFINITY, 0.0);
+	VIPS_ARG_DOUBLE(class, "max", 11, "Max", "Maximum value",
+		VIPS_ARGUMENT_OPTIONAL_INPUT, G_STRUCT_OFFSET(VipsArith2Hip, max), -INFINITY, INFINITY, 1.0);
+}
+
+static void
+vips_remainder_const_hip_args(VipsRemainderConstHipClass *class)
+{
+	VIPS_ARG_BOXED(class, "c", 201, "c", "Array of constants",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsArith2Hip, c), VIPS_TYPE_ARRAY_DOUBLE);
+}
+
+static void
+arith2_hip_init(VipsArith2Hip *arith)
+{
+	arith->round = VIPS_OPERATION_ROUND_RINT;
+	arith->min = 0.0;
+	arith->max = 1.0;
+}
+
+static void
+vips_round_hip_init(VipsRoundHip *arith)
+{
+	arith2_hip_init(arith);
+}
+
+static void
+vips_sign_hip_init(VipsSignHip *arith)
+{
+	arith2_hip_init(arith);
+}
+
+static void
+vips_clamp_hip_init(VipsClampHip *arith)
+{
+	arith2_hip_init(arith);
+}
+
+static void
+vips_remainder_const_hip_init(VipsRemainderConstHip *arith)
+{
+	arith2_hip_init(arith);
+}
+
+/* recomb_hip: conversion/recomb.c:207-240.  The matrix is read where the work starts, as conv_hip reads its mask: a
+ * handful of host doubles, not a streamed producer.  Matrices above 32 x 32 are the original's (hip_wants_original). */
+typedef struct _VipsRecombHip {
+	VipsHipOp parent_instance;
+	VipsImage *m;
+} VipsRecombHip;
+
+static int
+vips_recomb_hip_compute(VipsHipOp *op, VipsHipImage *in, VipsHipImage **out)
+{
+	VipsImage *M;
+	int result;
+
+	if (vips_check_matrix("recomb_hip", ((VipsRecombHip *) op)->m, &M))
+		return -1;
+	result = vips_hip_recomb_matrix(in, out, VIPS_MATRIX(M, 0, 0), M->Xsize, M->Ysize);
+	g_object_unref(M);
+
+	return result;
+}
+
+/* the plan is the matrix as doubles */
+static int
+vips_recomb_hip_strip_open(VipsHipOp *op, VipsImage *in, void **plan)
+{
+	VipsImage *M;
+
+	if (vips_check_matrix("recomb_hip", ((VipsRecombHip *) op)->m, &M))
+		return -1;
+	*plan = M;
+
+	return 0;
+}
+
+static int
+vips_recomb_hip_strip_run(VipsHipOp *op, void *plan, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	VipsImage *M = (VipsImage *) plan;
+
+	return vips_hip_recomb_gen(VIPS_MATRIX(M, 0, 0), M->Xsize, M->Ysize, in, out);
+}
+
+#define vips_recomb_hip_strip_need vips_linear_hip_strip_need
+#define vips_recomb_hip_strip_close vips_morph_hip_strip_close
+
+HIP_SUBCLASS_FULL(VipsRecombHip, vips_recomb_hip, "recomb_hip", "linear recombination with matrix (MI355X)", HIP_STRIPS(vips_recomb_hip))
+
+static void
+vips_recomb_hip_args(VipsRecombHipClass *class)
+{
+	VIPS_ARG_IMAGE(class, "m", 102, "M", "Matrix of coefficients",
+		VIPS_ARGUMENT_REQUIRED_INPUT, G_STRUCT_OFFSET(VipsRecombHip, m));
+}
+
+static void
+vips_recomb_hip_init(VipsRecombHip *recomb)
+{
+}
+
 /* relational_const_hip / boolean_const_hip / bandjoin_const_hip / extract_band_hip / bandmean_hip / bandbool_hip:
  * arithmetic/relational.c:560-585, boolean.c:553-576, conversion/bandjoin.c:395-421, extract.c:419-456,
  * bandmean.c:173-192, bandbool.c:218-246.  Pel by pel: an image over the HBM budget goes through in row strips of the

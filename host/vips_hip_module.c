@@ -1561,6 +1561,8 @@ hip_twin_header(VipsHipOp *op, VipsImage *out)
  *   - embed / gravity of pels of more than 32 bytes (the canvas kernels' ink), flatten to a background of more than
  *     256 bytes; replicate / wrap / grid of pels of more than 32 bytes (the cells kernels' pel);
  *   - linear with a vector of more than VIPS_HIP_ARITH_MAX_VECTOR elements (what the kernels keep in LDS);
+ *   - remainder_const of more than VIPS_HIP_ARITH_MAX_VECTOR bands or constants, recomb with a matrix above
+ *     VIPS_HIP_ARITH_MAX_VECTOR x VIPS_HIP_ARITH_MAX_VECTOR;
  *   - relational_const / boolean_const of more than VIPS_HIP_LOGIC_MAX_VECTOR bands or constants, bandjoin_const of no
  *     constants or of VIPS_HIP_BANDJOIN_MAX and more (the band kernel's source table).
  */
@@ -1648,6 +1650,30 @@ hip_wants_original(VipsHipOp *op, VipsImage *in)
 		}
 		if (strcmp(nick, "bandjoin_const_hip") == 0 ? (n < 1 || n >= VIPS_HIP_BANDJOIN_MAX)
 													: VIPS_MAX(n, in->Bands) > VIPS_HIP_LOGIC_MAX_VECTOR)
+			return TRUE;
+	}
+	if (strcmp(nick, "remainder_const_hip") == 0) {
+		VipsArrayDouble *c = NULL;
+		int n = 0;
+
+		g_object_get(op, "c", &c, NULL);
+		if (c) {
+			n = VIPS_AREA(c)->n;
+			vips_area_unref(VIPS_AREA(c));
+		}
+		if (VIPS_MAX(n, in->Bands) > VIPS_HIP_ARITH_MAX_VECTOR)
+			return TRUE;
+	}
+	if (strcmp(nick, "recomb_hip") == 0) {
+		VipsImage *m = NULL;
+		gboolean larger = FALSE;
+
+		g_object_get(op, "m", &m, NULL);
+		if (m) {
+			larger = m->Xsize > VIPS_HIP_ARITH_MAX_VECTOR || m->Ysize > VIPS_HIP_ARITH_MAX_VECTOR;
+			g_object_unref(m);
+		}
+		if (larger)
 			return TRUE;
 	}
 	if (strcmp(nick, "thumbnail_image_hip") == 0) {
@@ -1833,6 +1859,11 @@ g_module_check_init(GModule *module)
 	vips_linear_hip_get_type();
 	vips_invert_hip_get_type();
 	vips_abs_hip_get_type();
+	vips_round_hip_get_type();
+	vips_sign_hip_get_type();
+	vips_clamp_hip_get_type();
+	vips_remainder_const_hip_get_type();
+	vips_recomb_hip_get_type();
 	vips_relational_const_hip_get_type();
 	vips_boolean_const_hip_get_type();
 	vips_bandjoin_const_hip_get_type();

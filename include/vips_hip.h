@@ -1330,11 +1330,27 @@ typedef enum {
 	VIPS_HIP_ARITH_SUBTRACT,
 	VIPS_HIP_ARITH_MULTIPLY,
 	VIPS_HIP_ARITH_DIVIDE,
+	VIPS_HIP_ARITH_ROUND,
+	VIPS_HIP_ARITH_SIGN,
+	VIPS_HIP_ARITH_CLAMP,
+	VIPS_HIP_ARITH_MINPAIR,
+	VIPS_HIP_ARITH_MAXPAIR,
+	VIPS_HIP_ARITH_REMAINDER,
+	VIPS_HIP_ARITH_REMAINDER_CONST,
 	VIPS_HIP_ARITH_LAST
 } VipsHipArith;
 
+/* VipsOperationRound: the reference's values */
+typedef enum {
+	VIPS_HIP_ROUND_RINT = 0,
+	VIPS_HIP_ROUND_CEIL,
+	VIPS_HIP_ROUND_FLOOR,
+	VIPS_HIP_ROUND_LAST
+} VipsHipRound;
+
 /* The operation's format table (linear.c:425-428, invert.c:166-169, abs.c:188-191, add.c:180-183, subtract.c:176-179,
- * multiply.c:197-200, divide.c:199-202): the output format for an input (for two images: common) format; -1 for a
+ * multiply.c:197-200, divide.c:199-202, round.c:157-160, sign.c:162-165, clamp.c:139-142, minpair.c:139-142,
+ * maxpair.c:139-142, remainder.c:175-178): the output format for an input (for two images: common) format; -1 for a
  * complex or unknown format or operation.  Host only. */
 VIPS_HIP_API int vips_hip_arith_format(int op, int format);
 /* vips_linear_build restated (linear.c:121-209): the output's bands and format, whether the reference takes its
@@ -1373,6 +1389,84 @@ VIPS_HIP_API int vips_hip_add(VipsHipImage *left, VipsHipImage *right, VipsHipIm
 VIPS_HIP_API int vips_hip_subtract(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
 VIPS_HIP_API int vips_hip_multiply(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
 VIPS_HIP_API int vips_hip_divide(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+
+/* vips_round, vips_sign, vips_clamp, vips_minpair, vips_maxpair, vips_remainder and vips_remainder_const (round.c,
+ * sign.c, clamp.c, minpair.c, maxpair.c, remainder.c): further expressions of the same two kernels, planned by
+ * vips_hip_binary_plan (two images) and vips_hip_const_plan (constants), bit for bit the reference's values.
+ *   round      @round a VipsHipRound: rint / ceil / floor in the image's own type; an integer image is a copy.
+ *   sign       char, 1 / 0 / -1; a NaN gives -1.
+ *   clamp      VIPS_MAX(min, VIPS_MIN(max, pel)) with double bounds (the reference's defaults: 0 and 1), stored to the
+ *              image's format: a fractional bound on an integer image is truncated, a NaN pel comes through.
+ *   minpair, maxpair   the smaller / larger of two elements; for float and double fmin / fmax: a NaN loses to a number.
+ *   remainder  left % right in the common format, -1 (the format's maximum for unsigned formats) where the divisor is
+ *              0; for float and double a - b * floor(a / b) in double with a correctly rounded division.
+ *   remainder_const   the same against vips_hip_const_plan's c_int: fractional constants are truncated.
+ * Three corners in which the reference's behaviour is undefined are defined here and pinned to nothing:
+ *   - INT_MIN % -1 of int images (the reference traps) is 0, as every other value % -1 is;
+ *   - a clamp bound outside an integer format's range (the reference's out-of-range conversion) saturates at the
+ *     format's limits, so clamp never takes a value out of the interval a format can hold;
+ *   - minpair / maxpair of zeros of opposite sign: -0 counts as below +0 in either order (the reference's fmin and
+ *     fmax answer by the order of their arguments).
+ * The region forms work on a pair of windows of the same size; @out has the format vips_hip_arith_format gives and, for
+ * remainder_const, vips_hip_const_plan's bands. */
+VIPS_HIP_API int vips_hip_round_gen(int round, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_sign_gen(const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_clamp_gen(double min, double max, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_remainder_const_gen(const double *c, int n, const VipsHipRegion *in, const VipsHipRegion *out);
+VIPS_HIP_API int vips_hip_round(VipsHipImage *in, VipsHipImage **out, int round);
+VIPS_HIP_API int vips_hip_sign(VipsHipImage *in, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_clamp(VipsHipImage *in, VipsHipImage **out, double min, double max);
+VIPS_HIP_API int vips_hip_remainder_const(VipsHipImage *in, VipsHipImage **out, const double *c, int n);
+VIPS_HIP_API int vips_hip_minpair(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_maxpair(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_remainder(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out);
+
+/* vips_recomb (conversion/recomb.c): every pel's bands against a matrix, out[v] = sum_u m[v][u] * in[u]: colour
+ * matrices, sepia, greyscale by weights, channel mixes.  The sum starts at 0.0 and takes the products in order, in
+ * double, multiplies and adds separate; the result is float, double for a double image (the conversion rounds to
+ * nearest and overflows to an infinity).  The output has the matrix's height as its bands and everything else of the
+ * input's header.  Matrices of up to VIPS_HIP_ARITH_MAX_VECTOR x VIPS_HIP_ARITH_MAX_VECTOR; larger ones are refused by
+ * name.  ONE launch (recomb.hip): the streaming kernel for 3 -> 3, 3 -> 1, 1 -> 3, 4 -> 4, 4 -> 3 and 3 -> 4 bands of
+ * uchar, ushort or float with rows that start on dwords, otherwise (and under VIPS_HIP_NO_RECOMB_STREAM) the
+ * one-pel-a-lane kernel.
+ *
+ * vips_recomb_build's checks in its order and words (recomb.c:174-185: "image must be non-complex" for the image and
+ * for the matrix, "image must one band", "bands in must equal matrix width"), then the size limit; *@out_bands and
+ * *@out_format as recomb.c:195-197.  Host only. */
+VIPS_HIP_API int vips_hip_recomb_plan(int bands, int format, int mwidth, int mheight, int m_bands, int m_format,
+	int *out_bands, int *out_format);
+/* The generate function on a pair of windows of the same size; @m: @mheight rows of @mwidth doubles in host memory. */
+VIPS_HIP_API int vips_hip_recomb_gen(const double *m, int mwidth, int mheight, const VipsHipRegion *in,
+	const VipsHipRegion *out);
+/* Whole images.  vips_hip_recomb: @m a one-band image of any real format, turned to doubles as vips_check_matrix turns
+ * it; only its pels are read (a few doubles cross the bus). */
+VIPS_HIP_API int vips_hip_recomb_matrix(VipsHipImage *in, VipsHipImage **out, const double *m, int mwidth, int mheight);
+VIPS_HIP_API int vips_hip_recomb(VipsHipImage *in, VipsHipImage **out, VipsHipImage *m);
+/* 0: the threads of a block of the recomb kernels; 1: the most blocks a streaming launch has; 2: the most pels a lane of
+ * the streaming kernel takes at a time -- for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_recomb_step(int what);
+
+/* vips_sum (arithmetic/sum.c) and vips_bandrank (conversion/bandrank.c) over an array of 1 .. VIPS_HIP_BANDJOIN_MAX
+ * images ("<nickname>: arrays of more than 16 images are outside the HIP path" otherwise), aligned as the reference
+ * aligns them: the common format (vips__formatalike_vec; images that are not in it go through vips_hip_cast), one band
+ * against n (vips__bandalike_vec; a one-band image is indexed by pel), the largest size (vips__sizealike_vec; an image
+ * reads zero outside its own rectangle).  ONE launch (nary.hip): the streaming kernel for images of equal bands and
+ * size whose rows start on dwords, otherwise (and under VIPS_HIP_NO_NARY_STREAM) the one-element-a-lane kernel.
+ *   sum        accumulated in the output's type, image after image in index order: uint for the unsigned formats (it
+ *              wraps), int for the signed ones, float, double.
+ *   bandrank   the @index-th smallest of the n values of an element, in the common format; @index -1 is n / 2,
+ *              @index >= n "bandrank: index out of range"; one image is a copy.  Index 0 and n - 1 are the reference's
+ *              minimum and maximum loops: a NaN in the first image stays, a NaN later never wins.  The other indices
+ *              give the reference's value for inputs without NaN.
+ *
+ * The header of the result for @n images (@rank 0: sum, 1: bandrank): *@format the common format, *@out_format the
+ * result's, *@out_bands and *@interpretation by vips__bandalike_vec, the largest *@width and *@height, and *@out_index
+ * (may be NULL) the index bandrank uses.  Host only. */
+VIPS_HIP_API int vips_hip_nary_plan(int rank, int n, const int *widths, const int *heights, const int *bands,
+	const int *formats, const int *interpretations, int index, int *format, int *out_format, int *out_bands,
+	int *interpretation, int *width, int *height, int *out_index);
+VIPS_HIP_API int vips_hip_sum(VipsHipImage **in, int n, VipsHipImage **out);
+VIPS_HIP_API int vips_hip_bandrank(VipsHipImage **in, int n, VipsHipImage **out, int index);
 
 /* vips_stats: @out takes (bands + 1) * 10 doubles, row 0 over all bands, columns min, max, sum, sum2, avg, sd, xmin,
  * ymin, xmax, ymax (stats.c:91-103).  uchar, char, ushort, short and float images (the square of a 32-bit value does not

@@ -485,6 +485,25 @@ _SIGNATURES = {
     "vips_hip_subtract": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
     "vips_hip_multiply": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
     "vips_hip_divide": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_round_gen": (c_int, [c_int, RegionP, RegionP]),
+    "vips_hip_sign_gen": (c_int, [RegionP, RegionP]),
+    "vips_hip_clamp_gen": (c_int, [c_double, c_double, RegionP, RegionP]),
+    "vips_hip_remainder_const_gen": (c_int, [P(c_double), c_int, RegionP, RegionP]),
+    "vips_hip_round": (c_int, [c_void_p, P(c_void_p), c_int]),
+    "vips_hip_sign": (c_int, [c_void_p, P(c_void_p)]),
+    "vips_hip_clamp": (c_int, [c_void_p, P(c_void_p), c_double, c_double]),
+    "vips_hip_remainder_const": (c_int, [c_void_p, P(c_void_p), P(c_double), c_int]),
+    "vips_hip_minpair": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_maxpair": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_remainder": (c_int, [c_void_p, c_void_p, P(c_void_p)]),
+    "vips_hip_recomb_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P(c_int), P(c_int)]),
+    "vips_hip_recomb_gen": (c_int, [P(c_double), c_int, c_int, RegionP, RegionP]),
+    "vips_hip_recomb_matrix": (c_int, [c_void_p, P(c_void_p), P(c_double), c_int, c_int]),
+    "vips_hip_recomb": (c_int, [c_void_p, P(c_void_p), c_void_p]),
+    "vips_hip_recomb_step": (c_int, [c_int]),
+    "vips_hip_nary_plan": (c_int, [c_int, c_int] + [P(c_int)] * 5 + [c_int] + [P(c_int)] * 7),
+    "vips_hip_sum": (c_int, [P(c_void_p), c_int, P(c_void_p)]),
+    "vips_hip_bandrank": (c_int, [P(c_void_p), c_int, P(c_void_p), c_int]),
     "vips_hip_stats": (c_int, [c_void_p, P(c_double)]),
     "vips_hip_avg": (c_int, [c_void_p, P(c_double)]),
     "vips_hip_deviate": (c_int, [c_void_p, P(c_double)]),

@@ -1,5 +1,7 @@
 // vips_linear, vips_invert, vips_abs (arithmetic/linear.c, invert.c, abs.c), vips_add, vips_subtract, vips_multiply,
-// vips_divide (add.c, subtract.c, multiply.c, divide.c) and the scan of vips_stats (stats.c) on the device (gfx950).
+// vips_divide (add.c, subtract.c, multiply.c, divide.c), vips_round, vips_sign, vips_clamp, vips_minpair, vips_maxpair,
+// vips_remainder, vips_remainder_const (round.c, sign.c, clamp.c, minpair.c, maxpair.c, remainder.c) and the scan of
+// vips_stats (stats.c) on the device (gfx950).
 //
 // The pointwise operations are ONE launch that writes every output byte once: pointwise.h's stream kernel
 // (arith_stream) where the rows start on dwords on every side and every operand has the output's shape, its one-element-
@@ -117,6 +119,107 @@ VH_DEV OUT arith_elem(IN x, IN y, bool single, float a1, float b1, double ak, do
 	}
 }
 
+// a double to an integer format whose range holds it after truncation: the store's conversion of round.c, clamp.c
+template <typename T>
+VH_DEV T arith_store(double v)
+{
+	if constexpr (std::is_same<T, float>::value)
+		return (float) v;
+	else if constexpr (std::is_same<T, double>::value)
+		return v;
+	else {
+		// (a value outside the format's range: the reference's conversion is undefined; here it saturates)
+		constexpr double lo = std::is_unsigned<T>::value ? 0.0 : -(double) (1ull << (8 * sizeof(T) - 1));
+		constexpr double hi = std::is_unsigned<T>::value ? (double) ((1ull << (8 * sizeof(T) - 1)) - 1) * 2.0 + 1.0 : (double) ((1ull << (8 * sizeof(T) - 1)) - 1);
+		const double c = v < lo ? lo : v > hi ? hi : v;
+		return cvt_to<T, double>(c);
+	}
+}
+
+// fmin / fmax (minpair.c:73, maxpair.c:73): a NaN loses to a number.  Of zeros of opposite sign the reference's libm
+// returns one or the other by the order of its arguments; here -0 is below +0 in either order (IEEE 754's minimum and
+// maximum): equal operands differ in nothing but that sign, which min sets and max clears.
+template <bool MAX, typename F>
+VH_DEV F arith_fpair(F x, F y)
+{
+	typedef typename std::conditional<sizeof(F) == 4, unsigned int, u64>::type Bits;
+	if (x != x)
+		return y;
+	if (y != y)
+		return x;
+	if (x == y) {
+		const Bits bx = __builtin_bit_cast(Bits, x), by = __builtin_bit_cast(Bits, y);
+		return __builtin_bit_cast(F, MAX ? (Bits) (bx & by) : (Bits) (bx | by));
+	}
+	return (MAX ? x > y : x < y) ? x : y;
+}
+
+// One output element of round, sign, clamp, minpair, maxpair, remainder and remainder_const.  x, y: the operands;
+// round: ROUND_*; (ak, bk): clamp's min and max, or remainder_const's c_int[k] in ak.
+template <int OP, typename IN, typename OUT>
+VH_DEV OUT arith2_elem(IN x, IN y, int round, double ak, double bk)
+{
+	constexpr bool in_float = std::is_floating_point<IN>::value;
+	if constexpr (OP == ARITH_ROUND) {
+		// round.c:87-141: rint / ceil / floor in the image's own type; integer images are a copy (round.c:77-79)
+		if constexpr (std::is_same<IN, float>::value)
+			return round == ROUND_RINT ? __builtin_rintf(x) : round == ROUND_CEIL ? __builtin_ceilf(x) : __builtin_floorf(x);
+		else if constexpr (std::is_same<IN, double>::value)
+			return round == ROUND_RINT ? __builtin_rint(x) : round == ROUND_CEIL ? __builtin_ceil(x) : __builtin_floor(x);
+		else
+			return x;
+	}
+	else if constexpr (OP == ARITH_SIGN) {
+		// sign.c:86-102: a NaN is neither > 0 nor == 0
+		return x > (IN) 0 ? (OUT) 1 : x == (IN) 0 ? (OUT) 0 : (OUT) -1;
+	}
+	else if constexpr (OP == ARITH_CLAMP) {
+		// clamp.c:62-69: VIPS_MAX(min, VIPS_MIN(max, p)) with double bounds, then the store's conversion; the
+		// comparisons let a NaN pel through
+		const double v = (double) x;
+		const double inner = bk < v ? bk : v;
+		return arith_store<OUT>(ak > inner ? ak : inner);
+	}
+	else if constexpr (OP == ARITH_MINPAIR || OP == ARITH_MAXPAIR) {
+		// minpair.c:56-74, maxpair.c:56-74
+		if constexpr (in_float)
+			return arith_fpair<OP == ARITH_MAXPAIR, IN>(x, y);
+		else
+			return (OP == ARITH_MAXPAIR ? x > y : x < y) ? x : y;
+	}
+	else if constexpr (in_float) {
+		// remainder.c:106-118, :286-299: b ? a - b * floor(a / b) : -1 in double, the store rounds
+		const double a = (double) x;
+		double b;
+		if constexpr (OP == ARITH_REMAINDER)
+			b = (double) y;
+		else
+			b = ak;
+		return (OUT) (b != 0.0 ? a - __dmul_rn(b, __builtin_floor(__ddiv_rn(a, b))) : -1.0);
+	}
+	else if constexpr (OP == ARITH_REMAINDER) {
+		// remainder.c:94-102: p2 ? p1 % p2 : -1 (the format's maximum for the unsigned ones).  A divisor of -1
+		// leaves 0 whatever the dividend: the reference traps on INT_MIN % -1, here that is 0 too
+		if (y == (IN) 0)
+			return (OUT) -1;
+		if constexpr (std::is_signed<IN>::value)
+			return y == (IN) -1 ? (OUT) 0 : (OUT) ((int) x % (int) y);
+		else
+			return (OUT) ((unsigned int) x % (unsigned int) y);
+	}
+	else {
+		// remainder.c:273-282: c[b] ? p % c[b] : -1 with c an int: the usual conversions make c unsigned for a uint
+		// image and the pel an int for every other
+		const int c = cvt_i32(ak);
+		if (c == 0)
+			return (OUT) -1;
+		if constexpr (std::is_same<IN, unsigned int>::value)
+			return x % (unsigned int) c;
+		else
+			return c == -1 ? (OUT) 0 : (OUT) ((int) x % c);
+	}
+}
+
 // ---------------------------------------------------------------- the policy
 
 // vips_linear's band vectors from the kernel's arguments to LDS: thread i brings element i, picked by selects with
@@ -137,8 +240,6 @@ VH_DEV void arith_constants(const ArithArgs &a, double *ca, double *cb)
 	barrier();
 }
 
-constexpr bool arith_binary(int op) { return op >= ARITH_ADD; }
-
 template <int OP, typename IN_, typename OUT_>
 struct ArithOp {
 	typedef IN_ IN;
@@ -147,9 +248,16 @@ struct ArithOp {
 	typedef double CA, CB;
 	static constexpr int MAX_VECTOR = ARITH_MAX_VECTOR;
 	static constexpr bool binary = arith_binary(OP);
-	static constexpr bool constants = OP == ARITH_LINEAR;
+	// (clamp's two bounds and remainder_const's c_int reach elem() the way vips_linear's vectors do)
+	static constexpr bool constants = OP == ARITH_LINEAR || OP == ARITH_CLAMP || OP == ARITH_REMAINDER_CONST;
 	VH_DEV void stage(const ArithArgs &a, double *ca, double *cb) { arith_constants(a, ca, cb); }
-	VH_DEV OUT elem(const ArithArgs &a, IN l, IN r, double ak, double bk) { return arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk); }
+	VH_DEV OUT elem(const ArithArgs &a, IN l, IN r, double ak, double bk)
+	{
+		if constexpr (OP >= ARITH_ROUND)
+			return arith2_elem<OP, IN, OUT>(l, r, a.round, ak, bk);
+		else
+			return arith_elem<OP, IN, OUT>(l, r, a.single != 0, a.a1, a.b1f, ak, bk);
+	}
 };
 
 int arith_tile(int what)
@@ -174,7 +282,7 @@ int arith_run(const char *domain, int op, int in_format, int out_format, ArithAr
 		error(domain, "image rows too long");
 		return -1;
 	}
-	if (op == ARITH_LINEAR && !a.single && a.bands > ARITH_MAX_VECTOR) {
+	if ((op == ARITH_LINEAR || op == ARITH_REMAINDER_CONST) && !a.single && a.bands > ARITH_MAX_VECTOR) {
 		error(domain, "vectors of more than %d elements are outside the HIP path", ARITH_MAX_VECTOR);
 		return -1;
 	}
@@ -195,7 +303,18 @@ int arith_run(const char *domain, int op, int in_format, int out_format, ArithAr
 	GO(OP, UINT, u32, UINT, u32) GO(OP, INT, s32, INT, s32) GO(OP, FLOAT, f32, FLOAT, f32) GO(OP, DOUBLE, f64, DOUBLE, f64)
 	SAME(ARITH_INVERT)
 	SAME(ARITH_ABS)
+	// round.c:157-160, clamp.c:139-142, minpair.c:139-142, maxpair.c:139-142, remainder.c:175-178 (both forms)
+	SAME(ARITH_ROUND)
+	SAME(ARITH_CLAMP)
+	SAME(ARITH_MINPAIR)
+	SAME(ARITH_MAXPAIR)
+	SAME(ARITH_REMAINDER)
+	SAME(ARITH_REMAINDER_CONST)
 #undef SAME
+	// sign.c:162-165
+	GO(ARITH_SIGN, UCHAR, u8, CHAR, s8) GO(ARITH_SIGN, CHAR, s8, CHAR, s8) GO(ARITH_SIGN, USHORT, u16, CHAR, s8)
+	GO(ARITH_SIGN, SHORT, s16, CHAR, s8) GO(ARITH_SIGN, UINT, u32, CHAR, s8) GO(ARITH_SIGN, INT, s32, CHAR, s8)
+	GO(ARITH_SIGN, FLOAT, f32, CHAR, s8) GO(ARITH_SIGN, DOUBLE, f64, CHAR, s8)
 	// add.c:180-183, multiply.c:197-200
 #define SUM(OP) \
 	GO(OP, UCHAR, u8, USHORT, u16) GO(OP, CHAR, s8, SHORT, s16) GO(OP, USHORT, u16, UINT, u32) GO(OP, SHORT, s16, INT, s32) \

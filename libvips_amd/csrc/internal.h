@@ -500,17 +500,67 @@ struct BinaryOperands {
 typedef int (*BinaryPlanFn)(const void *closure, const _VipsHipImage *left, const _VipsHipImage *right, BinaryOperands *b);
 int binary_operands(const char *domain, _VipsHipImage *left, _VipsHipImage *right, BinaryPlanFn plan, const void *closure, BinaryOperands *b);
 // arith.hip: the pointwise operations of arithmetic/ (ops_arith.cpp checks everything)
-enum { ARITH_LINEAR = 0, ARITH_INVERT, ARITH_ABS, ARITH_ADD, ARITH_SUBTRACT, ARITH_MULTIPLY, ARITH_DIVIDE, ARITH_LAST };
+enum {
+	ARITH_LINEAR = 0, ARITH_INVERT, ARITH_ABS, ARITH_ADD, ARITH_SUBTRACT, ARITH_MULTIPLY, ARITH_DIVIDE,
+	ARITH_ROUND, ARITH_SIGN, ARITH_CLAMP, ARITH_MINPAIR, ARITH_MAXPAIR, ARITH_REMAINDER, ARITH_REMAINDER_CONST, ARITH_LAST
+};
+enum { ROUND_RINT = 0, ROUND_CEIL, ROUND_FLOOR, ROUND_LAST }; // VipsOperationRound
 constexpr int ARITH_MAX_VECTOR = 32; // elements of vips_linear's a and b once they differ from band to band
+// the operations with a right-hand image
+constexpr bool arith_binary(int op)
+{
+	return (op >= ARITH_ADD && op <= ARITH_DIVIDE) || (op >= ARITH_MINPAIR && op <= ARITH_REMAINDER);
+}
 struct ArithArgs : PointwiseGeom {
 	int single; // vips_linear: every element of a and of b the same (LOOP1, linear.c:213-223)
 	float a1, b1f; // ... those, as the float the reference makes of them
-	double a[ARITH_MAX_VECTOR], b[ARITH_MAX_VECTOR]; // a_ready, b_ready (linear.c:181-200)
+	int round; // vips_round: ROUND_*
+	// a_ready, b_ready (linear.c:181-200); vips_clamp: min in a[0], max in b[0]; vips_remainder_const: c_int in a
+	double a[ARITH_MAX_VECTOR], b[ARITH_MAX_VECTOR];
 };
 int arith_run(const char *domain, int op, int in_format, int out_format, ArithArgs a);
 // arith_tile: 0 the threads of a block, 1 the bytes of a group of the stream kernels, 2 / 3 the most blocks a pointwise /
 // a statistics launch has
 int arith_tile(int what);
+// recomb.hip: vips_recomb (conversion/recomb.c) on checked geometry (ops_recomb.cpp checks everything): every pel's
+// `mwidth` elements against the `mheight` rows of `matrix` (host memory, row-major), float out (double for double in)
+constexpr int RECOMB_MAX = 32; // columns and rows of the matrix
+constexpr int RECOMB_STREAM_MAX = 4; // ... of the shapes the stream kernel is compiled for
+struct RecombArgs {
+	const unsigned char *in;
+	unsigned char *out;
+	long long in_stride, out_stride; // bytes
+	int width, height; // pels, rows
+	int mwidth, mheight;
+	int runs; // (stream kernel) runs of pels of a row, the ragged one included
+	const double *matrix; // (general kernel) device memory
+	double m[RECOMB_STREAM_MAX * RECOMB_STREAM_MAX]; // (stream kernel) the coefficients, row-major
+};
+int recomb_run(const char *domain, int format, RecombArgs a, const double *matrix);
+// recomb_tile: 0 the threads of a block, 1 the most blocks of a stream launch, 2 the most pels of a stream kernel's run
+int recomb_tile(int what);
+// nary.hip: vips_sum (arithmetic/sum.c) and vips_bandrank (conversion/bandrank.c) over n images of one format on checked
+// geometry (ops_nary.cpp checks everything): ONE launch, the images' base pointers and strides in the kernel's
+// arguments.  Output element e of row y takes element e of every image's row, or -- an image of one band against
+// `bands` -- element e / bands; an image is zero right of its width and below its height (vips__sizealike).
+enum { NARY_SUM = 0, NARY_MIN, NARY_MAX, NARY_RANK, NARY_LAST }; // bandrank's index 0, n - 1 and any other
+constexpr int NARY_IMAGES = 16;
+struct NarySource {
+	const unsigned char *in;
+	long long stride; // bytes
+	int width, height, bands, pad;
+};
+struct NaryArgs {
+	unsigned char *out;
+	long long out_stride; // bytes
+	int elems, height, bands; // of the output
+	int n, index; // images; NARY_RANK: the index-th smallest
+	int groups; // (stream kernel) groups of an output row, the ragged one included
+	NarySource src[NARY_IMAGES];
+};
+int nary_run(const char *domain, int op, int format, NaryArgs a);
+// ops_logic.cpp: vips__bandalike_vec (arithmetic.c:210-254) over n images
+int bandalike(const char *domain, const int *bands, const int *interpretations, int n, int *out_bands, int *interpretation);
 // ... vips_stats' scan (stats.c:247-330) of a whole image of uchar, char, ushort, short or float: every block's
 // partial of every band goes to `slab` (blocks * bands entries, block-major), the host merges them in index order.
 // Sums of integer images are 64-bit integers, of float images doubles (as bits); extremes carry the raster index

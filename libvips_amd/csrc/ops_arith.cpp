@@ -1,5 +1,6 @@
-// vips_linear, vips_invert, vips_abs, vips_add, vips_subtract, vips_multiply, vips_divide, vips_stats, vips_avg,
-// vips_deviate, vips_min and vips_max (arithmetic/*.c) on images in HBM: the host side -- each build() restated (the
+// vips_linear, vips_invert, vips_abs, vips_add, vips_subtract, vips_multiply, vips_divide, vips_round, vips_sign,
+// vips_clamp, vips_minpair, vips_maxpair, vips_remainder, vips_remainder_const, vips_stats, vips_avg, vips_deviate,
+// vips_min and vips_max (arithmetic/*.c) on images in HBM: the host side -- each build() restated (the
 // format tables, vips_linear's vectors and its single-element rule, vips__formatalike / vips__bandalike /
 // vips__sizealike for two images, the errors with the reference's words), the merge of the statistics' partials and
 // the reference's avg / sd / row-0 expressions, the region checks, the C ABI.  The kernels are in arith.hip.
@@ -16,7 +17,8 @@ static_assert(ARITH_LAST == VIPS_HIP_ARITH_LAST, "one list of operations");
 
 namespace {
 
-const char *const NICKNAMES[ARITH_LAST] = { "linear", "invert", "abs", "add", "subtract", "multiply", "divide" };
+const char *const NICKNAMES[ARITH_LAST] = { "linear", "invert", "abs", "add", "subtract", "multiply", "divide", "round", "sign",
+	"clamp", "minpair", "maxpair", "remainder", "remainder_const" };
 
 } // namespace
 
@@ -183,6 +185,47 @@ int same_image(int op, VipsHipImage *in, VipsHipImage **out)
 	if (same_gen(op, &ri, &ro))
 		return -1;
 	*out = o.release();
+	return 0;
+}
+
+// round, sign, clamp and remainder_const on a pair of windows: `a` holds the operation's own arguments, the output has
+// `bands` bands of the format the operation's table gives for the input's
+int unary2_gen(int op, const VipsHipRegion *in, const VipsHipRegion *out, int bands, ArithArgs a)
+{
+	const char *domain = NICKNAMES[op];
+	const int format = vips_hip_arith_format(op, in->format);
+	if (out->bands != bands || out->format != format) {
+		error(domain, "the output must have %d bands of format %d", bands, format);
+		return -1;
+	}
+	if ((long long) out->width * out->bands >= (1LL << 31)) {
+		error(domain, "image rows too long");
+		return -1;
+	}
+	PointwiseGeom g;
+	pointwise_unary_geom(in, out, &g);
+	static_cast<PointwiseGeom &>(a) = g;
+	return arith_run(domain, op, in->format, out->format, a);
+}
+
+// ... how each of them starts
+int unary2_enter(int op, const VipsHipRegion *in, const VipsHipRegion *out, ArithArgs *a)
+{
+	if (ensure_init())
+		return -1;
+	if (arithmetic_window_pair(NICKNAMES[op], in, out))
+		return -1;
+	memset(a, 0, sizeof(*a));
+	a->single = 1;
+	return 0;
+}
+
+int check_round(int round)
+{
+	if (round < 0 || round >= ROUND_LAST) {
+		error("round", "bad operation %d", round);
+		return -1;
+	}
 	return 0;
 }
 
@@ -355,6 +398,13 @@ int vips_hip_arith_format(int op, int format)
 		/* subtract.c:176-179 */ { S, S, I, I, I, I, F, X, D, DX },
 		/* multiply.c:197-200 */ { US, S, UI, I, UI, I, F, X, D, DX },
 		/* divide.c:199-202 */ { F, F, F, F, F, F, F, X, D, DX },
+		/* round.c:157-160 */ { UC, C, US, S, UI, I, F, X, D, DX },
+		/* sign.c:162-165 */ { C, C, C, C, C, C, C, X, C, DX },
+		/* clamp.c:139-142 */ { UC, C, US, S, UI, I, F, X, D, DX },
+		/* minpair.c:139-142 */ { UC, C, US, S, UI, I, F, X, D, DX },
+		/* maxpair.c:139-142 */ { UC, C, US, S, UI, I, F, X, D, DX },
+		/* remainder.c:175-178 */ { UC, C, US, S, UI, I, F, X, D, DX },
+		/* ... and remainder_const */ { UC, C, US, S, UI, I, F, X, D, DX },
 	};
 	if (op < 0 || op >= ARITH_LAST || format < 0 || format > VIPS_HIP_FORMAT_DPCOMPLEX || format_iscomplex(format))
 		return -1;
@@ -423,7 +473,7 @@ int vips_hip_binary_plan(int op, int left_width, int left_height, int left_bands
 	int right_width, int right_height, int right_bands, int right_format, int right_interpretation, int *format,
 	int *out_format, int *bands, int *interpretation, int *width, int *height)
 {
-	if (op < ARITH_ADD || op >= ARITH_LAST) {
+	if (!arith_binary(op)) {
 		error("arithmetic", "not a binary operation: %d", op);
 		return -1;
 	}
@@ -567,6 +617,119 @@ int vips_hip_multiply(VipsHipImage *left, VipsHipImage *right, VipsHipImage **ou
 int vips_hip_divide(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out)
 {
 	return binary_image(ARITH_DIVIDE, left, right, out);
+}
+
+int vips_hip_round_gen(int round, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	ArithArgs a;
+	if (unary2_enter(ARITH_ROUND, in, out, &a) || check_round(round))
+		return -1;
+	a.round = round;
+	return unary2_gen(ARITH_ROUND, in, out, in->bands, a);
+}
+
+int vips_hip_sign_gen(const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	ArithArgs a;
+	if (unary2_enter(ARITH_SIGN, in, out, &a))
+		return -1;
+	return unary2_gen(ARITH_SIGN, in, out, in->bands, a);
+}
+
+int vips_hip_clamp_gen(double min, double max, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	ArithArgs a;
+	if (unary2_enter(ARITH_CLAMP, in, out, &a))
+		return -1;
+	a.a[0] = min;
+	a.b[0] = max;
+	return unary2_gen(ARITH_CLAMP, in, out, in->bands, a);
+}
+
+int vips_hip_remainder_const_gen(const double *c, int n, const VipsHipRegion *in, const VipsHipRegion *out)
+{
+	const char *domain = NICKNAMES[ARITH_REMAINDER_CONST];
+	ArithArgs a;
+	if (unary2_enter(ARITH_REMAINDER_CONST, in, out, &a))
+		return -1;
+	int bands;
+	// (the plan writes one element a band of the output: the larger of n and the input's bands)
+	std::vector<int> ci((size_t) ARITH_MAX_VECTOR + (size_t) in->bands + (size_t) (n > 0 ? n : 0));
+	if (vips_hip_const_plan(domain, c, n, in->bands, in->format, &bands, nullptr, ci.data(), nullptr))
+		return -1;
+	for (int i = 1; i < bands; i++)
+		if (ci[i] != ci[0])
+			a.single = 0;
+	if (!a.single && bands > ARITH_MAX_VECTOR) {
+		error(domain, "vectors of more than %d elements are outside the HIP path", ARITH_MAX_VECTOR);
+		return -1;
+	}
+	// remainder.c:277, :290: both loops read c_int
+	for (int i = 0; i < ARITH_MAX_VECTOR && i < bands; i++)
+		a.a[i] = (double) ci[i];
+	return unary2_gen(ARITH_REMAINDER_CONST, in, out, bands, a);
+}
+
+int vips_hip_round(VipsHipImage *in, VipsHipImage **out, int round)
+{
+	const char *domain = NICKNAMES[ARITH_ROUND];
+	if (enter(domain, in, out))
+		return -1;
+	if (arithmetic_noncomplex(domain, in->format) || check_round(round))
+		return -1;
+	// round.c:77-79: vips_unary_copy, a pointer copy
+	if (in->format <= VIPS_HIP_FORMAT_INT)
+		return vips_hip_cast(in, out, in->format);
+	return whole_image(in, out, in->bands, in->format,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_round_gen(round, ri, ro); });
+}
+
+int vips_hip_sign(VipsHipImage *in, VipsHipImage **out)
+{
+	const char *domain = NICKNAMES[ARITH_SIGN];
+	if (enter(domain, in, out))
+		return -1;
+	if (arithmetic_noncomplex(domain, in->format))
+		return -1;
+	return whole_image(in, out, in->bands, vips_hip_arith_format(ARITH_SIGN, in->format), vips_hip_sign_gen);
+}
+
+int vips_hip_clamp(VipsHipImage *in, VipsHipImage **out, double min, double max)
+{
+	const char *domain = NICKNAMES[ARITH_CLAMP];
+	if (enter(domain, in, out))
+		return -1;
+	if (arithmetic_noncomplex(domain, in->format))
+		return -1;
+	return whole_image(in, out, in->bands, in->format,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_clamp_gen(min, max, ri, ro); });
+}
+
+int vips_hip_remainder_const(VipsHipImage *in, VipsHipImage **out, const double *c, int n)
+{
+	const char *domain = NICKNAMES[ARITH_REMAINDER_CONST];
+	if (enter(domain, in, out))
+		return -1;
+	int bands;
+	if (vips_hip_const_plan(domain, c, n, in->bands, in->format, &bands, nullptr, nullptr, nullptr))
+		return -1;
+	return whole_image(in, out, bands, in->format,
+		[&](const VipsHipRegion *ri, const VipsHipRegion *ro) { return vips_hip_remainder_const_gen(c, n, ri, ro); });
+}
+
+int vips_hip_minpair(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out)
+{
+	return binary_image(ARITH_MINPAIR, left, right, out);
+}
+
+int vips_hip_maxpair(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out)
+{
+	return binary_image(ARITH_MAXPAIR, left, right, out);
+}
+
+int vips_hip_remainder(VipsHipImage *left, VipsHipImage *right, VipsHipImage **out)
+{
+	return binary_image(ARITH_REMAINDER, left, right, out);
 }
 
 int vips_hip_stats(VipsHipImage *in, double *out)

@@ -51,8 +51,10 @@ int check_output(const char *domain, const VipsHipRegion *out, int bands, int fo
 }
 
 // vips__bandalike_vec (arithmetic.c:210-254) over n images: the most bands of any, the interpretation of the LAST image
-// that has them, and the header's interpretation of image 0 once it is matched
-int bandalike(const char *domain, const int *bands, const int *interpretations, int n, int *out_bands, int *interpretation)
+// that has them, and the header's interpretation of image 0 once it is matched (shared with ops_nary.cpp)
+} // namespace
+
+int vh::bandalike(const char *domain, const int *bands, const int *interpretations, int n, int *out_bands, int *interpretation)
 {
 	int most = 1, type = interpretations[0];
 	for (int i = 0; i < n; i++)
@@ -69,6 +71,8 @@ int bandalike(const char *domain, const int *bands, const int *interpretations, 
 	*interpretation = bands[0] == most ? interpretations[0] : type;
 	return 0;
 }
+
+namespace {
 
 struct ConstCall {
 	int family, op;

@@ -717,6 +717,95 @@ class Image(object):
         """vips_divide: 0 where ``other`` is 0."""
         return self._binary(lib.vips_hip_divide, other)
 
+    # vips_round / vips_sign / vips_clamp, vips_minpair / vips_maxpair, vips_remainder / vips_remainder_const
+    ROUND = {"rint": 0, "ceil": 1, "floor": 2}
+
+    def round(self, round):
+        """vips_round: ``"rint"``, ``"ceil"`` or ``"floor"`` in the image's own type; an integer image is a copy."""
+        return self._unary(lib.vips_hip_round, _enum(self.ROUND, round, "round"))
+
+    def rint(self):
+        return self.round("rint")
+
+    def ceil(self):
+        return self.round("ceil")
+
+    def floor(self):
+        return self.round("floor")
+
+    def sign(self):
+        """vips_sign: char, 1 / 0 / -1; a NaN gives -1."""
+        return self._unary(lib.vips_hip_sign)
+
+    def clamp(self, min=0.0, max=1.0):
+        """vips_clamp: the larger of ``min`` and the smaller of ``max`` and the pel, stored to the image's format."""
+        return self._unary(lib.vips_hip_clamp, float(min), float(max))
+
+    def minpair(self, other):
+        """vips_minpair: the smaller of the two images' elements; a NaN loses to a number."""
+        return self._binary(lib.vips_hip_minpair, other)
+
+    def maxpair(self, other):
+        return self._binary(lib.vips_hip_maxpair, other)
+
+    def remainder(self, other):
+        """vips_remainder / vips_remainder_const: ``self % other``, -1 where the divisor is 0; numbers are truncated to
+        int, as the reference truncates them."""
+        if isinstance(other, Image):
+            return self._binary(lib.vips_hip_remainder, other)
+        c = self._numbers(other)
+        return self._unary(lib.vips_hip_remainder_const, c.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), len(c))
+
+    __mod__ = remainder
+
+    # vips_sum / vips_bandrank, as pyvips spells them: sum is called on the class with the whole array, bandrank on the
+    # first image with the others
+    @staticmethod
+    def _array(images, what):
+        images = list(images)
+        if not images or not all(isinstance(im, Image) for im in images):
+            raise TypeError("%s: need a list of images" % what)
+        return (ctypes.c_void_p * len(images))(*[im._h for im in images]), len(images)
+
+    @staticmethod
+    def sum(images):
+        """vips_sum: the images added up in order, in uint / int / float / double; formats, bands (one against n) and
+        sizes are matched as the reference matches them."""
+        handles, n = Image._array(images, "sum")
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_sum(handles, n, ctypes.byref(out)))
+        return Image(out.value)
+
+    def bandrank(self, other, index=-1):
+        """vips_bandrank of self and an image or a list of images: element by element the ``index``-th smallest of the
+        images' values (-1: the median)."""
+        images = [self] + (list(other) if isinstance(other, (list, tuple)) else [other])
+        handles, n = Image._array(images, "bandrank")
+        out = ctypes.c_void_p()
+        check(lib.vips_hip_bandrank(handles, n, ctypes.byref(out), int(index)))
+        return Image(out.value)
+
+    # vips_recomb
+    @staticmethod
+    def recomb_matrix(m):
+        """A nested list or a numpy array as recomb's matrix: a contiguous (mheight, mwidth) array of doubles."""
+        a = np.ascontiguousarray(m, np.float64)
+        if a.ndim == 1:
+            a = a[None, :]
+        if a.ndim == 3 and a.shape[2] == 1:
+            a = a[:, :, 0]
+        if a.ndim != 2 or a.size == 0:
+            raise ValueError("recomb: need a 2D matrix")
+        return np.ascontiguousarray(a)
+
+    def recomb(self, m):
+        """vips_recomb: every pel's bands against the matrix ``m`` (an ``Image`` of one band, a nested list or a numpy
+        array, one row an output band): float, double for a double image."""
+        if isinstance(m, Image):
+            return self._unary(lib.vips_hip_recomb, m._h)
+        a = self.recomb_matrix(m)
+        return self._unary(lib.vips_hip_recomb_matrix, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), a.shape[1], a.shape[0])
+
     def stats(self):
         """vips_stats: a (bands + 1, 10) array, row 0 over all bands, columns min, max, sum, sum2, avg, sd, xmin, ymin,
         xmax, ymax."""
