@@ -344,6 +344,10 @@ VIPS_HIP_API int vips_hip_zoom_gen(const VipsHipRegion *in, const VipsHipRegion 
  * size in / fac; what vips_resize uses for the integer part of a nearest-neighbour shrink
  * (resize.c:165-203). */
 VIPS_HIP_API int vips_hip_subsample_gen(const VipsHipRegion *in, const VipsHipRegion *out, int xfac, int yfac);
+/* 0: the threads of a block of the upsize, zoom and subsample kernels (a pel a lane); 1: the most blocks a launch has
+ * (the blocks of a row times the rows in flight; the other rows are taken in turns) -- for tests that want sizes
+ * round them. */
+VIPS_HIP_API int vips_hip_upsize_step(int what);
 
 /* -------------------------------------------------------------- convolution */
 
@@ -371,6 +375,10 @@ VIPS_HIP_API int vips_hip_conv_out_format(const VipsHipConv *conv, int format);
  */
 VIPS_HIP_API int vips_hip_conv_gen(const VipsHipConv *conv,
 	const VipsHipRegion *in, const VipsHipRegion *out);
+/* 0: the threads of a block of the convolution kernels; 1: the most rows the one-element-a-lane kernel has in flight
+ * (its blocks take the other rows in turns); 2: the most rows of blocks the register-tiled, grouped and row-streaming
+ * kernels launch: taller outputs go to the one-element-a-lane kernel -- for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_conv_step(int what);
 
 /* precision=approximate.  Host-side state of one vips_conva (convolution/conva.c:676-767: the
  * rint()ed mask cut into `layers` slabs, every slab row a run of ones, near-identical runs
@@ -403,6 +411,9 @@ VIPS_HIP_API int vips_hip_conva_gen(const VipsHipConva *plan,
  */
 VIPS_HIP_API int vips_hip_convasep_gen(const VipsHipConva *plan,
 	const VipsHipRegion *in, const VipsHipRegion *out, int vertical);
+/* 0: the threads of a block of the approximate convolutions' kernels; 1: the most rows a launch has in flight (its
+ * blocks take the other rows in turns). */
+VIPS_HIP_API int vips_hip_conva_step(int what);
 
 /* vips_gaussmat (create/gaussmat.c:95-167).  Writes at most @max doubles,
  * returns the mask width (height is 1 when separable, else == width), or -1.
@@ -478,6 +489,13 @@ VIPS_HIP_API int vips_hip_premultiply_gen(const VipsHipRegion *in, const VipsHip
 VIPS_HIP_API int vips_hip_rot_gen(int angle, const VipsHipRegion *in, const VipsHipRegion *out);
 VIPS_HIP_API int vips_hip_flip_gen(int direction, const VipsHipRegion *in, const VipsHipRegion *out);
 VIPS_HIP_API int vips_hip_rot_tile_side(int pel_size);
+/* 0: the threads of a block of the streaming and the one-pel-a-lane kernel; 1: the most blocks a launch of either has
+ * (the blocks of a row times the rows in flight; the other rows are taken in turns) -- for tests that want sizes round
+ * them. */
+VIPS_HIP_API int vips_hip_rot_step(int what);
+/* The bytes a lane of the streaming kernel takes at a time for @pel_size: 48 for a mirror of pels that do not divide
+ * 16, else 16 (a row-permuted copy moves rows of bytes: pel size 1); 0 for pel sizes the kernel is not compiled for. */
+VIPS_HIP_API int vips_hip_rot_group(int pel_size);
 
 /* ----------------------------------------------------------------- morphology
  *
@@ -565,7 +583,8 @@ VIPS_HIP_API int vips_hip_stdif_step(int what);
  * the fused kernel's tile take two vips_hip_conv_gen passes and the gate edge_combine_u8: the same pixels.)
  * The input window must hold the out rect grown by one pel all round, clipped to the image: rows
  * vips_hip_edge_need() names.  vips_hip_edge_step: 0 / 1 the elements of a row / the rows a block of the fused kernel
- * makes, 2 the widest pel (bands) it takes (3 .. 5: the same for vips_hip_canny_gen's kernel, below).
+ * makes, 2 the widest pel (bands) it takes (3 .. 5: the same for vips_hip_canny_gen's kernel, below), 6 the most rows
+ * the combining kernels (edge_combine_*, compass_combine) have in flight: their blocks take the other rows in turns.
  */
 typedef enum {
 	VIPS_HIP_EDGE_SOBEL = 0,
@@ -821,7 +840,9 @@ VIPS_HIP_API int vips_hip_hist_find(VipsHipImage *in, VipsHipImage **out, int ba
 /* The kernel under it: the histograms of @n (1 .. 6) rectangles of @in -- @rects holds left, top, width, height
  * for each -- in ONE launch and one copy back; @counts (host memory) takes 256 * bands counters a rectangle,
  * the count of value v in band b at [v * bands + b].  vips_hip_hist_step: what the kernel takes at a time, for
- * tests that want sizes round it (0: the bytes of a row a wave takes in a step; 1: the rows a block takes). */
+ * tests that want sizes round it (0: the bytes of a row a wave takes in a step; 1: the rows a block takes; 2 / 3:
+ * the most blocks a histogram launch, all rectangles together, / a vips_hip_maplut launch has: a wave takes the rows
+ * beyond them in turns). */
 VIPS_HIP_API int vips_hip_hist_rects(VipsHipImage *in, const int *rects, int n, unsigned int *counts);
 VIPS_HIP_API int vips_hip_hist_step(int what);
 /* vips_maplut (histogram/maplut.c:612-760) of a uchar image: out = lut[in], band by band.  @lut is an image one row
@@ -1080,7 +1101,8 @@ VIPS_HIP_API int vips_hip_mapim_gen(const VipsHipRegion *in_region, const VipsHi
 	const VipsHipRegion *out_region, const VipsHipMapim *args, int in_width, int in_height);
 /* The kernels' units, for tests that want sizes round them: 0 / 1 the pels / rows of a block's patch of the output,
  * 2 / 3 of a wave's patch, 4 the most blocks a bounds launch has, 5 the threads of a block of the bounds and xyz
- * kernels, 6 the bytes of a group of the xyz kernel; -1 for anything else. */
+ * kernels, 6 the bytes of a group of the xyz kernel, 7 the most blocks an xyz launch has (its lanes take the other
+ * groups in turns; the bounds pass shares these blocks out between a row's pels and the rows); -1 for anything else. */
 VIPS_HIP_API int vips_hip_mapim_step(int what);
 /* vips_xyz (create/xyz.c) in two dimensions: a two-band uint image of interpretation multiband whose pel (x, y) holds
  * (x, y), made on the device. */
@@ -1224,7 +1246,9 @@ VIPS_HIP_API int vips_hip_insert(VipsHipImage *main, VipsHipImage *sub, VipsHipI
 VIPS_HIP_API int vips_hip_join(VipsHipImage *in1, VipsHipImage *in2, VipsHipImage **out, int direction,
 	const VipsHipInsert *args);
 /* 0: the threads of a block of the canvas kernels; 1: the bytes of a group of the streaming kernel for @pel_size
- * (0: that pel size takes the one-pel-a-lane kernel), for tests that want sizes round them. */
+ * (0: that pel size takes the one-pel-a-lane kernel); 2: the most blocks a launch has (a streaming launch's blocks, whose
+ * lanes take the other groups in turns; the blocks of a row times the rows in flight of the one-pel-a-lane kernels,
+ * which take the other rows in turns) -- for tests that want sizes round them. */
 VIPS_HIP_API int vips_hip_canvas_step(int what, int pel_size);
 
 /* ------------------------------------------------ sheets and tiles: arrayjoin, replicate, wrap, grid; zoom, subsample
@@ -1296,7 +1320,9 @@ VIPS_HIP_API int vips_hip_grid_gen(int tile_height, int across, const VipsHipReg
 VIPS_HIP_API int vips_hip_zoom(VipsHipImage *in, VipsHipImage **out, int xfac, int yfac);
 VIPS_HIP_API int vips_hip_subsample(VipsHipImage *in, VipsHipImage **out, int xfac, int yfac);
 /* 0: the threads of a block of the cells kernels; 1: the bytes of a group of the streaming kernel for @pel_size
- * (0: that pel size takes the one-pel-a-lane kernel), for tests that want sizes round them. */
+ * (0: that pel size takes the one-pel-a-lane kernel); 2: the most blocks a launch has (a streaming launch's blocks, whose
+ * lanes take the other groups in turns; the blocks of a row times the rows in flight of the one-pel-a-lane kernels,
+ * which take the other rows in turns) -- for tests that want sizes round them. */
 VIPS_HIP_API int vips_hip_cells_step(int what, int pel_size);
 
 /* ------------------------------------------------ arithmetic: linear / invert / abs, add / subtract / multiply / divide,
@@ -1467,6 +1493,11 @@ VIPS_HIP_API int vips_hip_nary_plan(int rank, int n, const int *widths, const in
 	int *interpretation, int *width, int *height, int *out_index);
 VIPS_HIP_API int vips_hip_sum(VipsHipImage **in, int n, VipsHipImage **out);
 VIPS_HIP_API int vips_hip_bandrank(VipsHipImage **in, int n, VipsHipImage **out, int index);
+/* 0: the threads of a block of the n-ary kernels; 1: the most blocks a launch has (a streaming launch's blocks, the
+ * blocks of a row times the rows in flight of the one-element-a-lane kernel); 2: the bytes of the output a lane of the
+ * streaming kernel makes at a time for sum and for bandrank's first and last index; 3 / 4: for bandrank's other indices
+ * on formats of up to four bytes / on double -- for tests that want sizes round them. */
+VIPS_HIP_API int vips_hip_nary_step(int what);
 
 /* vips_stats: @out takes (bands + 1) * 10 doubles, row 0 over all bands, columns min, max, sum, sum2, avg, sd, xmin,
  * ymin, xmax, ymax (stats.c:91-103).  uchar, char, ushort, short and float images (the square of a 32-bit value does not
@@ -1679,6 +1710,9 @@ VIPS_HIP_API int vips_hip_labelregions_step(int what);
  * divisions in its order on the host.  Any real format and any number of bands; complex images are refused by name, and
  * so are images of more than 2^25 pels along the count (the reference's uint sums could wrap there). */
 VIPS_HIP_API int vips_hip_countlines(VipsHipImage *in, int direction, double *nolines);
+/* 0: the threads of a block of the countlines kernel (an element a lane); 1: the rows of a block's strip; 2: the most
+ * blocks a launch has: the blocks of a row times the strips in flight, the other strips in turns. */
+VIPS_HIP_API int vips_hip_countlines_step(int what);
 
 #ifdef __cplusplus
 }

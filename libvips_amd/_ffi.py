@@ -260,6 +260,7 @@ _SIGNATURES = {
     "vips_hip_affine_out_size": (c_int, [c_int, c_double]),
     "vips_hip_zoom_gen": (c_int, [RegionP, RegionP, c_int, c_int]),
     "vips_hip_subsample_gen": (c_int, [RegionP, RegionP, c_int, c_int]),
+    "vips_hip_upsize_step": (c_int, [c_int]),
     "vips_hip_reduce_gen": (c_int, [c_void_p, c_void_p, RegionP, RegionP]),
     "vips_hip_reduce_gen_tiled": (c_int, [c_void_p, c_void_p, RegionP, RegionP, c_int]),
     # shrink
@@ -273,6 +274,8 @@ _SIGNATURES = {
     "vips_hip_conv_get_vector": (c_int, [c_void_p, P(c_int), P(c_int), P(c_int), c_int]),
     "vips_hip_conv_out_format": (c_int, [c_void_p, c_int]),
     "vips_hip_conv_gen": (c_int, [c_void_p, RegionP, RegionP]),
+    "vips_hip_conv_step": (c_int, [c_int]),
+    "vips_hip_conva_step": (c_int, [c_int]),
     "vips_hip_vector_set_enabled": (None, [c_int]),
     "vips_hip_vector_isenabled": (c_int, []),
     "vips_hip_set_exact_float": (None, [c_int]),
@@ -351,6 +354,8 @@ _SIGNATURES = {
     "vips_hip_rot_gen": (c_int, [c_int, RegionP, RegionP]),
     "vips_hip_flip_gen": (c_int, [c_int, RegionP, RegionP]),
     "vips_hip_rot_tile_side": (c_int, [c_int]),
+    "vips_hip_rot_step": (c_int, [c_int]),
+    "vips_hip_rot_group": (c_int, [c_int]),
     "vips_hip_rot": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_flip": (c_int, [c_void_p, P(c_void_p), c_int]),
     "vips_hip_autorot": (c_int, [c_void_p, P(c_void_p), P(c_int), P(c_int)]),
@@ -504,6 +509,7 @@ _SIGNATURES = {
     "vips_hip_nary_plan": (c_int, [c_int, c_int] + [P(c_int)] * 5 + [c_int] + [P(c_int)] * 7),
     "vips_hip_sum": (c_int, [P(c_void_p), c_int, P(c_void_p)]),
     "vips_hip_bandrank": (c_int, [P(c_void_p), c_int, P(c_void_p), c_int]),
+    "vips_hip_nary_step": (c_int, [c_int]),
     "vips_hip_stats": (c_int, [c_void_p, P(c_double)]),
     "vips_hip_avg": (c_int, [c_void_p, P(c_double)]),
     "vips_hip_deviate": (c_int, [c_void_p, P(c_double)]),
@@ -549,6 +555,7 @@ _SIGNATURES = {
     "vips_hip_labelregions": (c_int, [c_void_p, P(c_void_p), P(c_int)]),
     "vips_hip_labelregions_step": (c_int, [c_int]),
     "vips_hip_countlines": (c_int, [c_void_p, c_int, P(c_double)]),
+    "vips_hip_countlines_step": (c_int, [c_int]),
 }
 
 MISSING = []

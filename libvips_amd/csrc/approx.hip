@@ -684,11 +684,13 @@ convasep_float_kernel(ApproxArgs a)
 	}
 }
 
+constexpr int APPROX_GRID_ROWS = 32768; // the most rows a launch has in flight (grid.y); the others in turns
+
 template <typename K>
 static int approx_launch(K kernel, const ApproxArgs &a, const char *name)
 {
 	const int ne = a.out_width * a.epp;
-	dim3 grid((ne + 255) / 256, a.out_height < 32768 ? a.out_height : 32768, 1);
+	dim3 grid((ne + 255) / 256, a.out_height < APPROX_GRID_ROWS ? a.out_height : APPROX_GRID_ROWS, 1);
 	Gate gate(name);
 	hipLaunchKernelGGL(kernel, grid, dim3(256, 1, 1), 0, stream(), a);
 	VH_CHECK(hipGetLastError());
@@ -1104,6 +1106,15 @@ int vips_hip_convasep_gen(const VipsHipConva *plan, const VipsHipRegion *in, con
 	}
 	error("convasep", "unsupported band format %d", in->format);
 	return -1;
+}
+
+int vips_hip_conva_step(int what)
+{
+	switch (what) {
+	case 0: return 256;
+	case 1: return vh::APPROX_GRID_ROWS;
+	default: return 0;
+	}
 }
 
 } // extern "C"

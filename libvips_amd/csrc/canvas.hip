@@ -264,6 +264,7 @@ int canvas_tile(int what, int pel)
 	switch (what) {
 	case 0: return CANVAS_THREADS;
 	case 1: return pel >= 1 && pel <= 16 ? canvas_group_of(pel) : 0;
+	case 2: return POINTWISE_GRID_BLOCKS;
 	default: return 0;
 	}
 }

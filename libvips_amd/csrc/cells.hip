@@ -263,6 +263,7 @@ int cells_tile(int what, int pel)
 	switch (what) {
 	case 0: return CELLS_THREADS;
 	case 1: return pel >= 1 && pel <= 16 ? cells_group_of(pel) : 0;
+	case 2: return POINTWISE_GRID_BLOCKS;
 	default: return 0;
 	}
 }

@@ -132,12 +132,15 @@ conv_general(ConvArgs a)
 	}
 }
 
+constexpr int CONV_GENERAL_ROWS = 32768; // the most rows conv_general has in flight (grid.y); the others in turns
+constexpr int CONV_GRID_ROWS = 65535;    // the most rows of blocks the other kernels launch: above it they step aside
+
 template <typename TIN, typename TOUT, int MODE>
 static int launch_conv(const ConvArgs &a, const char *gate_name)
 {
 	const int ne = a.out_width * a.epp;
 	dim3 block(256, 1, 1);
-	dim3 grid((ne + 255) / 256, a.out_height < 32768 ? a.out_height : 32768, 1);
+	dim3 grid((ne + 255) / 256, a.out_height < CONV_GENERAL_ROWS ? a.out_height : CONV_GENERAL_ROWS, 1);
 	Gate gate(gate_name);
 	hipLaunchKernelGGL((conv_general<TIN, TOUT, MODE>), grid, block, 0, stream(), a);
 	VH_CHECK(hipGetLastError());
@@ -332,14 +335,14 @@ static int launch_conv_tiled(const ConvArgs &a, const char *gate_name)
 	if (a.mask_width == 1) {
 		const int ne = a.out_width * a.epp;
 		dim3 grid((ne + 255) / 256, (a.out_height + CONV_TILE - 1) / CONV_TILE, 1);
-		if (grid.y > 65535)
+		if (grid.y > CONV_GRID_ROWS)
 			return 1;
 		hipLaunchKernelGGL((conv_tiled<TIN, TOUT, MODE, true>), grid, block, 0, stream(), a);
 	}
 	else {
 		const int ids = ((a.out_width + CONV_TILE - 1) / CONV_TILE) * a.epp;
 		dim3 grid((ids + 255) / 256, a.out_height, 1);
-		if (grid.y > 65535)
+		if (grid.y > CONV_GRID_ROWS)
 			return 1;
 		hipLaunchKernelGGL((conv_tiled<TIN, TOUT, MODE, false>), grid, block, 0, stream(), a);
 	}
@@ -624,7 +627,7 @@ static int launch_convf_rows_lds(const ConvArgs &a, const char *name, bool fuse)
 {
 	constexpr int R = 4;
 	dim3 grid((a.out_width + CONVF_LDS_SPAN - 1) / CONVF_LDS_SPAN, (a.out_height + R - 1) / R, 1);
-	if (grid.y > 65535)
+	if (grid.y > CONV_GRID_ROWS)
 		return 1;
 	Gate gate(name);
 	if (!fuse)
@@ -651,7 +654,7 @@ static int launch_conv_best(const ConvArgs &a, const char *name, bool fuse = fal
 		}
 	}
 	if constexpr (MODE == 2 && std::is_integral<TIN>::value) {
-		if (a.mask_width >= 8 && a.out_height <= 65535 && a.dense8 && !getenv("VIPS_HIP_NO_GROUPED_CONV")) {
+		if (a.mask_width >= 8 && a.out_height <= CONV_GRID_ROWS && a.dense8 && !getenv("VIPS_HIP_NO_GROUPED_CONV")) {
 			const int ids = ((a.out_width + CONV_TILE - 1) / CONV_TILE) * a.epp;
 			dim3 grid((ids + 255) / 256, a.out_height, 1);
 			Gate gate(name);
@@ -678,7 +681,7 @@ static int launch_conv_best(const ConvArgs &a, const char *name, bool fuse = fal
 			return 0;
 		}
 	}
-	if (a.mask_width * a.mask_height >= 3 && a.out_height <= 65535 * (a.mask_width == 1 ? CONV_TILE : 1)) {
+	if (a.mask_width * a.mask_height >= 3 && a.out_height <= CONV_GRID_ROWS * (a.mask_width == 1 ? CONV_TILE : 1)) {
 		if constexpr (MODE == 0 && sizeof(TIN) <= 2) {
 			if (a.narrow) {
 				const int r = launch_conv_tiled<TIN, TOUT, 3>(a, name);
@@ -1130,6 +1133,16 @@ int vips_hip_gaussmat(double sigma, double min_ampl, int separable, int precisio
 	if (scale)
 		*scale = sum;
 	return width;
+}
+
+int vips_hip_conv_step(int what)
+{
+	switch (what) {
+	case 0: return 256;
+	case 1: return vh::CONV_GENERAL_ROWS;
+	case 2: return vh::CONV_GRID_ROWS;
+	default: return 0;
+	}
 }
 
 } // extern "C"

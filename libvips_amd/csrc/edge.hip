@@ -40,6 +40,7 @@ namespace vh {
 constexpr int EDGE_THREADS = 256;
 constexpr int EDGE_TW = 4 * EDGE_THREADS; // elements = bytes
 constexpr int EDGE_TH = 16;               // rows
+constexpr int EDGE_COMBINE_ROWS = 65535;   // the most rows the combining kernels have in flight (grid.y)
 constexpr int EDGE_LDS_MAX = 64 * 1024;
 
 struct EdgeArgs {
@@ -179,6 +180,8 @@ int edge_tile(int what)
 			bands++;
 		return bands;
 	}
+	if (what == 3)
+		return EDGE_COMBINE_ROWS;
 	return 0;
 }
 
@@ -236,7 +239,7 @@ int edge_combine_run(const char *domain, const void *c1, long long c1_stride, co
 	a.height = height;
 	long long blocks = (elems + EDGE_THREADS - 1) / EDGE_THREADS;
 	blocks = blocks > 4096 ? 4096 : blocks;
-	const dim3 grid((unsigned int) blocks, (unsigned int) (height > 65535 ? 65535 : height), 1);
+	const dim3 grid((unsigned int) blocks, (unsigned int) (height > EDGE_COMBINE_ROWS ? EDGE_COMBINE_ROWS : height), 1);
 	{
 		Gate gate(is_float ? "edge_combine_f32" : "edge_combine_u8");
 		if (is_float)
@@ -511,7 +514,7 @@ int compass_combine_run(const char *domain, const void *in, long long in_stride,
 	a.times = times;
 	long long blocks = (elems + EDGE_THREADS - 1) / EDGE_THREADS;
 	blocks = blocks > 4096 ? 4096 : blocks;
-	const dim3 grid((unsigned int) blocks, (unsigned int) (height > 65535 ? 65535 : height), 1);
+	const dim3 grid((unsigned int) blocks, (unsigned int) (height > EDGE_COMBINE_ROWS ? EDGE_COMBINE_ROWS : height), 1);
 	{
 		Gate gate("compass_combine");
 		switch (format) {

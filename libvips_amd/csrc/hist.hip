@@ -339,10 +339,17 @@ int maplut_run(const char *domain, MaplutArgs a)
 
 extern "C" {
 
-// what the kernel takes at a time: 0 the bytes of a row a wave takes in a step, 1 the rows a block takes in a step
+// what the kernel takes at a time: 0 the bytes of a row a wave takes in a step, 1 the rows a block takes in a step,
+// 2 / 3 the most blocks a histogram launch (all rectangles together) / a maplut launch has
 int vips_hip_hist_step(int what)
 {
-	return what == 0 ? vh::HIST_WAVE_BYTES : what == 1 ? vh::HIST_WAVES : 0;
+	switch (what) {
+	case 0: return vh::HIST_WAVE_BYTES;
+	case 1: return vh::HIST_WAVES;
+	case 2: return vh::HIST_GRID_BLOCKS;
+	case 3: return vh::MAPLUT_GRID_BLOCKS;
+	default: return 0;
+	}
 }
 
 } // extern "C"

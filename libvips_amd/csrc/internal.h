@@ -417,7 +417,7 @@ struct CanvasArgs {
 };
 int canvas_run(const char *domain, CanvasArgs a);
 // canvas_tile: 0 the threads of a block, 1 the bytes of a group of the stream kernel for a pel size (0: the stream
-// kernel does not take it)
+// kernel does not take it), 2 the most blocks a launch has
 int canvas_tile(int what, int pel);
 // ... vips_flatten's generate functions (flatten.c:167-419): `format` uchar takes the table kernels, everything else the
 // double macros; `black` the black-background path.  `ink` holds bands - 1 elements of `format`.
@@ -559,6 +559,10 @@ struct NaryArgs {
 	NarySource src[NARY_IMAGES];
 };
 int nary_run(const char *domain, int op, int format, NaryArgs a);
+// nary_tile: 0 the threads of a block, 1 the most blocks a launch has (a stream launch's blocks, the blocks_x * grid.y of
+// a general one), 2 the bytes of the output a lane of the stream kernel makes at a time for sum and bandrank's minimum
+// and maximum, 3 / 4 for bandrank's other indices on formats of up to four bytes / on double
+int nary_tile(int what);
 // ops_logic.cpp: vips__bandalike_vec (arithmetic.c:210-254) over n images
 int bandalike(const char *domain, const int *bands, const int *interpretations, int n, int *out_bands, int *interpretation);
 // ... vips_stats' scan (stats.c:247-330) of a whole image of uchar, char, ushort, short or float: every block's

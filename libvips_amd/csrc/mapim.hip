@@ -358,6 +358,7 @@ int mapim_tile(int what)
 	case 4: return MAPIM_BOUNDS_BLOCKS;
 	case 5: return MAPIM_THREADS;
 	case 6: return POINTWISE_GROUP;
+	case 7: return POINTWISE_GRID_BLOCKS;
 	default: return -1;
 	}
 }

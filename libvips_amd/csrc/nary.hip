@@ -285,6 +285,18 @@ static int nary_launch(const char *domain, NaryArgs a)
 	return 0;
 }
 
+int nary_tile(int what)
+{
+	switch (what) {
+	case 0: return POINTWISE_THREADS;
+	case 1: return POINTWISE_GRID_BLOCKS;
+	case 2: return nary_group<NARY_SUM, u32>();
+	case 3: return nary_group<NARY_RANK, u8>();
+	case 4: return nary_group<NARY_RANK, f64>();
+	default: return 0;
+	}
+}
+
 // Everything has been checked (ops_nary.cpp).
 int nary_run(const char *domain, int op, int format, NaryArgs a)
 {

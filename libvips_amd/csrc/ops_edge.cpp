@@ -192,7 +192,7 @@ void vips_hip_edge_need(int top, int height, int *in_top, int *in_height)
 
 int vips_hip_edge_step(int what)
 {
-	return what < 3 ? edge_tile(what) : canny_tile(what - 3);
+	return what == 6 ? edge_tile(3) : what < 3 ? edge_tile(what) : canny_tile(what - 3);
 }
 
 static int edge_image(VipsHipImage *in, VipsHipImage **out, int edge)

@@ -164,4 +164,9 @@ int vips_hip_bandrank(VipsHipImage **in, int n, VipsHipImage **out, int index)
 	return nary_image(1, in, n, out, index);
 }
 
+int vips_hip_nary_step(int what)
+{
+	return nary_tile(what);
+}
+
 } // extern "C"

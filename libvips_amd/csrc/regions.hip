@@ -640,3 +640,13 @@ int regions_tile(int what)
 }
 
 } // namespace vh
+
+extern "C" int vips_hip_countlines_step(int what)
+{
+	switch (what) {
+	case 0: return vh::REGIONS_THREADS;
+	case 1: return vh::COUNTLINES_ROWS;
+	case 2: return vh::COUNTLINES_GRID_BLOCKS;
+	default: return 0;
+	}
+}

@@ -278,10 +278,12 @@ rot_general_kernel(RotArgs a)
 
 // ---------------------------------------------------------------- dispatch
 
+constexpr int ROT_GRID_BLOCKS = 256 * 8; // of a launch of the row-preserving kernels
+
 static int rows_grid_of(int blocks_x, int rows)
 {
 	// enough blocks to fill the part, rows dealt round-robin over grid.y
-	int gy = (256 * 8 + blocks_x - 1) / blocks_x;
+	int gy = (ROT_GRID_BLOCKS + blocks_x - 1) / blocks_x;
 	gy = gy < 1 ? 1 : gy;
 	return gy > rows ? rows : gy;
 }
@@ -478,6 +480,25 @@ int vips_hip_rot_tile_side(int pel_size)
 	switch (pel_size) {
 	case 1: case 2: case 3: case 4: case 6: case 8: case 12: case 16:
 		return vh::rot_tile_side_of(pel_size);
+	default:
+		return 0;
+	}
+}
+
+int vips_hip_rot_step(int what)
+{
+	switch (what) {
+	case 0: return vh::ROT_THREADS;
+	case 1: return vh::ROT_GRID_BLOCKS;
+	default: return 0;
+	}
+}
+
+int vips_hip_rot_group(int pel_size)
+{
+	switch (pel_size) {
+	case 1: case 2: case 3: case 4: case 6: case 8: case 12: case 16:
+		return vh::flip_chunk_of(pel_size);
 	default:
 		return 0;
 	}

@@ -30,6 +30,8 @@
 
 namespace vh {
 
+constexpr int UPSIZE_THREADS = 256; // of a block: a pel a lane
+
 // TRANSFORM_SCALE (64), INTERPOLATE_SHIFT (12), INTERPOLATE_SCALE: resample.h; BicubicTables, the rounding helpers and the
 // interpolators (interp_pel): interp_device.h
 
@@ -58,7 +60,7 @@ static __device__ __forceinline__ T fetch(const UpsizeArgs &a, int ex, int ey, i
 }
 
 template <typename T, int INTERP>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(UPSIZE_THREADS)
 upsize_kernel(UpsizeArgs a)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -96,7 +98,7 @@ upsize_kernel(UpsizeArgs a)
 // clamped column offsets and the horizontal coefficients once per thread.  The same integer arithmetic in the same
 // order.
 template <int B>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(UPSIZE_THREADS)
 upsize_bicubic_u8_walk(UpsizeArgs a, int seg)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -173,7 +175,7 @@ upsize_bicubic_u8_walk(UpsizeArgs a, int seg)
 }
 
 template <typename T>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(UPSIZE_THREADS)
 zoom_kernel(UpsizeArgs a, int xfac, int yfac)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -191,7 +193,7 @@ zoom_kernel(UpsizeArgs a, int xfac, int yfac)
 
 // vips_subsample (conversion/subsample.c): out(x, y) = in(x * xfac, y * yfac)
 template <typename T>
-__global__ void __launch_bounds__(256)
+__global__ void __launch_bounds__(UPSIZE_THREADS)
 subsample_kernel(UpsizeArgs a, int xfac, int yfac)
 {
 	const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -298,9 +300,11 @@ static TabPtr column_table(const TabKey &key, int full_width)
 	return p;
 }
 
+constexpr int UPSIZE_GRID_BLOCKS = 16384; // of a launch of upsize, zoom and subsample
+
 static int rows_grid(int gx, int height)
 {
-	int gy = 16384 / (gx > 0 ? gx : 1);
+	int gy = UPSIZE_GRID_BLOCKS / (gx > 0 ? gx : 1);
 	gy = gy < 1 ? 1 : gy;
 	return height < gy ? height : gy;
 }
@@ -308,8 +312,8 @@ static int rows_grid(int gx, int height)
 template <typename T>
 static int launch_upsize(const UpsizeArgs &a, int interpolate)
 {
-	dim3 block(256, 1, 1);
-	const int gx = (a.out_width + 255) / 256;
+	dim3 block(UPSIZE_THREADS, 1, 1);
+	const int gx = (a.out_width + UPSIZE_THREADS - 1) / UPSIZE_THREADS;
 	dim3 grid(gx, rows_grid(gx, a.out_height), 1);
 	if (interpolate == VIPS_HIP_INTERPOLATE_BICUBIC && std::is_same<T, unsigned char>::value && a.bands >= 1 && a.bands <= 4 &&
 		!getenv("VIPS_HIP_NO_UPSIZE_WALK")) {
@@ -344,8 +348,8 @@ static int launch_upsize(const UpsizeArgs &a, int interpolate)
 template <typename T>
 static int launch_subsample(const UpsizeArgs &a, int xfac, int yfac)
 {
-	dim3 block(256, 1, 1);
-	const int gx = (a.out_width + 255) / 256;
+	dim3 block(UPSIZE_THREADS, 1, 1);
+	const int gx = (a.out_width + UPSIZE_THREADS - 1) / UPSIZE_THREADS;
 	dim3 grid(gx, rows_grid(gx, a.out_height), 1);
 	Gate gate("subsample");
 	hipLaunchKernelGGL((subsample_kernel<T>), grid, block, 0, stream(), a, xfac, yfac);
@@ -356,8 +360,8 @@ static int launch_subsample(const UpsizeArgs &a, int xfac, int yfac)
 template <typename T>
 static int launch_zoom(const UpsizeArgs &a, int xfac, int yfac)
 {
-	dim3 block(256, 1, 1);
-	const int gx = (a.out_width + 255) / 256;
+	dim3 block(UPSIZE_THREADS, 1, 1);
+	const int gx = (a.out_width + UPSIZE_THREADS - 1) / UPSIZE_THREADS;
 	dim3 grid(gx, rows_grid(gx, a.out_height), 1);
 	Gate gate("zoom");
 	hipLaunchKernelGGL((zoom_kernel<T>), grid, block, 0, stream(), a, xfac, yfac);
@@ -545,6 +549,15 @@ int vips_hip_subsample_gen(const VipsHipRegion *in, const VipsHipRegion *out, in
 	}
 	error(domain, "unsupported band format %d", in->format);
 	return -1;
+}
+
+int vips_hip_upsize_step(int what)
+{
+	switch (what) {
+	case 0: return vh::UPSIZE_THREADS;
+	case 1: return vh::UPSIZE_GRID_BLOCKS;
+	default: return 0;
+	}
 }
 
 } // extern "C"

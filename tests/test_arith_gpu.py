@@ -430,6 +430,54 @@ def test_pointwise_grid_stride():
     same(got, src.astype(np.uint16) * other, "multiply")
 
 
+VECTOR_A, VECTOR_B = [1.1, 1.1, -2.5], [-20.3, 7.25, 300.0]
+
+
+@pytest.mark.parametrize("case", ["invert", "linear-ushort-to-uchar", "linear-uchar-to-float"])
+def test_second_turn_of_the_stream_in_frames(case):
+    """Rows that stay rows: a window of a larger frame whose rows together have more 16-byte groups than the capped grid
+    has lanes, so that a lane's second group is on another row, at another place of it and at another phase of the band
+    vector; every row ends in a ragged group, and nothing outside the window is written."""
+    dtype, out_dtype = {"invert": (np.uint8, np.uint8), "linear-ushort-to-uchar": (np.uint16, np.uint8),
+                        "linear-uchar-to-float": (np.uint8, np.float32)}[case]
+    lanes = lib.vips_hip_arith_step(2) * lib.vips_hip_arith_step(0)
+    per_group = lib.vips_hip_arith_step(1) // np.dtype(out_dtype).itemsize
+    width = (4096 // np.dtype(out_dtype).itemsize + 3 + 2) // 3
+    groups = -(-width * 3 // per_group)
+    height = lanes // groups + 9
+    assert width * 3 % per_group and height > 1 and groups * height > lanes
+    # the lane's second group is elsewhere in its row, at another phase of the three constants
+    assert lanes % groups and lanes % groups * per_group % 3
+    src = noise(width, height, dtype, 3, 421)
+    if case == "invert":
+        call, want = lib.vips_hip_invert_gen, model_invert(src)
+    else:
+        args = Image.linear_args(VECTOR_A, VECTOR_B, out_dtype == np.uint8)
+        call, want = (lambda i, o: lib.vips_hip_linear_gen(ctypes.byref(args), i, o)), model_linear(src, VECTOR_A, VECTOR_B, out_dtype == np.uint8)
+    with gated() as g:
+        got = gen_in_frames(src, out_dtype, 3, call, 4)
+    assert g.ran == {"arith_stream": 1}, g.ran
+    same(got, want, case)
+
+
+@pytest.mark.parametrize("case", [(1, 3, 3), (3, 2, 3), (3, 2, 1)], ids=lambda c: "%dblocks-%dbands" % (c[0], c[2]))
+def test_second_turn_of_the_general_kernel(case):
+    """The one-element-a-lane kernel with more rows than grid.y, which is the cap for rows of one block and a third of it
+    for rows of three (the last ragged); one band against a three-vector reaches it without the switch."""
+    blocks, extra, bands = case
+    threads, cap = lib.vips_hip_arith_step(0), lib.vips_hip_arith_step(2)
+    width = ((blocks - 1) * threads + 63) // 3
+    in_flight = -(-cap // -(-width * 3 // threads))
+    rows = in_flight + extra
+    assert -(-width * 3 // threads) == blocks and rows > in_flight and (blocks == 1) == (in_flight == cap) and width * 3 % threads
+    src = noise(width, rows, np.uint16, bands, 431)
+    args = Image.linear_args(VECTOR_A, VECTOR_B, False)
+    with general_kernel(bands == 3), gated() as g:
+        got = gen_in_frames(src, np.float32, 3, lambda i, o: lib.vips_hip_linear_gen(ctypes.byref(args), i, o), 4)
+    assert g.ran == {"arith_general": 1}, g.ran
+    same(got, model_linear(src if bands == 3 else np.repeat(src, 3, axis=2), VECTOR_A, VECTOR_B, False), case)
+
+
 # ---------------------------------------------------------------- two images: the reference's command line
 
 OPS = ["add", "subtract", "multiply", "divide"]

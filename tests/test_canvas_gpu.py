@@ -526,6 +526,92 @@ def test_addalpha(dtype):
     same(rgba.gravity("centre", 15, 9).flatten().numpy(), model_embed(src, 3, 2, 15, 9, "black"), "round trip")
 
 
+# ---------------------------------------------------------------- the capped grids' second turn
+
+def rows_over_the_grid(blocks_x, extra):
+    """(rows a launch of blocks_x blocks a row has in flight, `extra` more than that)."""
+    in_flight = -(-lib.vips_hip_canvas_step(2, 0) // blocks_x)
+    return in_flight, in_flight + extra
+
+
+def narrow_width(blocks, per_lane=1):
+    """Pels whose row takes `blocks` blocks of lanes of per_lane pels, the last block ragged."""
+    threads = lib.vips_hip_canvas_step(0, 0)
+    width = ((blocks - 1) * threads + 41) * per_lane - (per_lane - 1)
+    assert -(-(-(-width // per_lane)) // threads) == blocks and -(-width // per_lane) % threads
+    return width
+
+
+@pytest.mark.parametrize("case", [(4, "mirror"), (3, "repeat"), (4, "background")], ids=lambda c: "pel%d-%s" % c)
+def test_canvas_stream_second_turn(case):
+    """A canvas of more 16-byte (RGBA) / 48-byte (RGB) groups than the capped grid has lanes, every row ending in a
+    ragged group: the lanes' second group lies in rows that hold the image's last rows with the borders left and right
+    of them, its bottom edge, and the mirrored / repeated border or the ink below it."""
+    pel, extend = case
+    dtype, bands = PELS[pel]
+    lanes = lib.vips_hip_canvas_step(2, pel) * lib.vips_hip_canvas_step(0, pel)
+    per_group = lib.vips_hip_canvas_step(1, pel) // pel
+    cw = 2069 if pel == 4 else 2068
+    groups = -(-cw // per_group)
+    first_step = lanes // groups  # whole rows of it
+    ch = first_step + 140
+    assert cw % per_group and cw * pel % 4 == 0 and groups * ch > lanes
+    x, y, w, h = 9, first_step - 500, 2040, 560
+    assert first_step < y + h - 20 and y + h + 40 < ch and w * pel % 4 == 0
+    src = noise(w, h, dtype, bands, 171)
+    background = [10, 200, 30, 77][:bands] if extend == "background" else None
+    args = embed_args(x, y, cw, ch, extend, background)
+    with gated() as g:
+        both(lambda: dev_embed(src, x, y, cw, ch, extend, background), lambda: Ref.run("embed", src, args), args)
+    assert g.ran == {"canvas_stream": 1}, g.ran
+
+
+@pytest.mark.parametrize("case", [(3, 1, "mirror"), (2, 3, "repeat"), (4, 1, "copy"), (8, 3, "background"), (24, 1, "mirror")],
+                         ids=lambda c: "pel%d-%dblocks-%s" % c)
+def test_canvas_general_second_turn(case):
+    """The one-pel-a-lane kernel with more rows than grid.y (the cap for a canvas one block wide, a third of it for
+    three), copying units of 1, 2, 4 and 8 bytes: the image's last rows, its bottom edge and the border below it -- a
+    mirrored, a repeated, a copied one, the ink -- lie in the second turn, with the borders left and right of them."""
+    pel, blocks, extend = case
+    dtype, bands = PELS[pel]
+    cw = narrow_width(blocks)
+    in_flight, ch = rows_over_the_grid(blocks, 60)
+    assert ch > in_flight and (blocks == 1) == (in_flight == lib.vips_hip_canvas_step(2, pel))
+    x, y, w, h = 7, in_flight // 2, cw - 15, in_flight - in_flight // 2 + 20
+    assert in_flight < y + h < ch
+    src = noise(w, h, dtype, bands, 151)
+    background = [10, 200, 30, 77][:bands] if extend == "background" else None
+    args = embed_args(x, y, cw, ch, extend, background)
+    with general_kernel(), gated() as g:
+        both(lambda: dev_embed(src, x, y, cw, ch, extend, background), lambda: Ref.run("embed", src, args), args)
+    assert g.ran == {"canvas_general": 1}, g.ran
+
+
+@pytest.mark.parametrize("case", [("flatten_u8", np.uint8, 4, 1), ("flatten_u8", np.uint8, 4, 3), ("flatten_u8", np.uint8, 2, 3),
+                                  ("flatten_any", np.uint16, 4, 1), ("flatten_any", np.float32, 2, 3),
+                                  ("addalpha", np.uint8, 3, 1), ("addalpha", np.uint16, 1, 3)],
+                         ids=lambda c: "%s-%s_x%d-%dblocks" % (c[0], np.dtype(c[1]).name, c[2], c[3]))
+def test_flatten_and_addalpha_second_turn(case):
+    """Narrow and tall: more rows than grid.y for rows of one block and of three.  Four-band uchar images with rows on
+    dwords take flatten_u8's four-pels-a-lane form, two-band ones its one-pel-a-lane form."""
+    family, dtype, bands, blocks = case
+    quad = family == "flatten_u8" and bands == 4
+    width = narrow_width(blocks, 4 if quad else 1)
+    in_flight, rows = rows_over_the_grid(blocks, 5 - blocks)
+    assert rows > in_flight and (blocks == 1) == (in_flight == lib.vips_hip_canvas_step(2, 0))
+    src = noise(width, rows, dtype, bands, 161)
+    if np.dtype(dtype).kind == "f":
+        src[:, :, -1] = np.abs(src[:, :, -1]) % 256  # an alpha inside 0 .. max_alpha
+    interp = "rgb16" if dtype == np.uint16 and bands > 2 else ("srgb" if bands > 2 else "b-w")
+    if family == "addalpha":
+        with gated() as g:
+            both(lambda: Image.new_from_array(src, interp).addalpha(),
+                 lambda: Ref.run_interp("addalpha", src, "", interpretation=INTERP[interp]), case)
+        assert g.ran == {"addalpha": 1}, g.ran
+    else:
+        check_flatten(src, [12, 200, 77][:bands - 1], interp=INTERP[interp], family=family)
+
+
 # ---------------------------------------------------------------- insert / join: the reference's command line
 
 def ref_cli(tmp_path, op, images, positional, options):

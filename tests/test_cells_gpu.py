@@ -436,6 +436,77 @@ def test_zoom_and_subsample_against_the_reference():
         Image.new_from_array(noise(8, 8, np.uint8, 1, 802)).subsample(9, 1)
 
 
+# ---------------------------------------------------------------- 6a. the capped grids' second turn
+
+@pytest.mark.parametrize("pel", [4, 3])
+def test_cells_stream_second_turn(tmp_path, pel):
+    """A sheet of more 16-byte (RGBA) / 48-byte (RGB) groups than the capped grid has lanes, two cells across with a shim
+    between them: the lanes' second group lies in the last row of cells, which holds a cell's edges, the shim, an image's
+    bottom edge inside its box and the box no image fills; every row of the sheet ends in a ragged group."""
+    dtype, bands = PELS[pel]
+    lanes = lib.vips_hip_cells_step(2, pel) * lib.vips_hip_cells_step(0, pel)
+    per_group = lib.vips_hip_cells_step(1, pel) // pel
+    hspacing, shim, vspacing = 1028, 13 if pel == 4 else 12, 70
+    width = 2 * hspacing + shim
+    groups = -(-width // per_group)
+    rows_of_cells = lanes // groups // (vspacing + shim) + 2
+    height = rows_of_cells * (vspacing + shim) - shim
+    assert width % per_group and width * pel % 4 == 0 and groups * height > lanes
+    # the first step ends above the last row of cells
+    assert lanes // groups < height - vspacing
+    n = 2 * rows_of_cells - 1
+    arrays = [noise(1024 if i % 3 else 1028, vspacing - 8 * (i % 2) - 3 * (i == n - 1), dtype, bands, 900 + i) for i in range(n)]
+    kw = dict(across=2, shim=shim, halign="centre", valign="low", hspacing=hspacing, vspacing=vspacing, background=[10, 200, 30, 77][:bands])
+    want, _ = model.ref_arrayjoin(tmp_path, [(a, INTERP["srgb"]) for a in arrays], model.cli_options(**kw))
+    assert want.shape == (height, width, bands)
+    got, _, ran = dev_arrayjoin(arrays, **kw)
+    assert ran == {"cells_stream": 1}, ran
+    same(got, want, ("second turn", pel))
+
+
+@pytest.mark.parametrize("case", [(3, 1), (2, 3), (4, 1), (8, 3), (24, 1)], ids=lambda c: "pel%d-%dblocks" % c)
+def test_cells_general_second_turn(case):
+    """The one-pel-a-lane kernel with more rows than grid.y (the cap for a sheet one block wide, a third of it for three
+    blocks), copying units of 1, 2, 4 and 8 bytes: cells' edges, shims and images' bottom edges in the second turn."""
+    pel, blocks = case
+    dtype, bands = PELS[pel]
+    threads, cap = lib.vips_hip_cells_step(0, pel), lib.vips_hip_cells_step(2, pel)
+    hspacing, shim = ((blocks - 1) * threads + 40) // 2, 1
+    width = 2 * hspacing + shim
+    in_flight = -(-cap // blocks)
+    vspacing = in_flight // 3
+    height = 4 * (vspacing + shim) - shim
+    assert -(-width // threads) == blocks and width % 2 and height > in_flight + vspacing and (blocks == 1) == (in_flight == cap)
+    arrays = [noise(hspacing - i % 3, vspacing - 5 * (i % 2), dtype, bands, 920 + i) for i in range(7)]
+    kw = dict(across=2, shim=shim, halign="high", valign="centre", hspacing=hspacing, vspacing=vspacing, background=[10, 200, 30, 77][:bands])
+    with general_kernel():
+        got, _, ran = dev_arrayjoin(arrays, **kw)
+    assert ran == {"cells_general": 1}, ran
+    want = model_arrayjoin(arrays, **kw)
+    assert want.shape == (height, width, bands)
+    same(got, want, ("second turn", pel, blocks))
+
+
+@pytest.mark.parametrize("blocks", [1, 3])
+@pytest.mark.parametrize("nick", ["zoom", "subsample"])
+def test_zoom_and_subsample_second_turn(nick, blocks):
+    """Narrow and tall: more output rows than a launch has in flight -- the block budget over the blocks of a row,
+    rounded down -- for rows of one block and of three (the last ragged)."""
+    threads, cap = lib.vips_hip_upsize_step(0), lib.vips_hip_upsize_step(1)
+    in_flight = cap // blocks
+    xfac, yfac = 3, 2
+    out_width, out_height = ((blocks - 1) * threads + 42) // xfac * xfac, (in_flight + 5) // yfac * yfac
+    assert -(-out_width // threads) == blocks and out_width % threads and out_height > in_flight
+    dtype, bands, interp = ((np.uint8, 3, "srgb"), (np.uint8, 1, "b-w"))[blocks // 2]
+    if nick == "zoom":
+        src = noise(out_width // xfac, out_height // yfac, dtype, bands, 940)
+    else:
+        src = noise(out_width * xfac + 1, out_height * yfac + 1, dtype, bands, 941)
+    got = both(lambda: getattr(Image.new_from_array(src, interp), nick)(xfac, yfac),
+               lambda: model.ref_input(nick, src, "xfac=%d,yfac=%d" % (xfac, yfac), INTERP[interp]), (nick, blocks), (nick,))
+    assert (got.height, got.width) == (out_height, out_width)
+
+
 # ---------------------------------------------------------------- 7. the region forms
 
 def need_of(fn, *args):

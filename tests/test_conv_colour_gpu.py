@@ -672,3 +672,97 @@ def test_sharpen_adaptive_large_mixed(params, raw, monkeypatch):
         want = PortCC.sharpen(src, "srgb", **params)
     bad = np.argwhere((got != want).any(axis=-1))
     assert len(bad) == 0, (len(bad), bad[:5].tolist())
+
+
+# ---- the row caps of conv.hip and approx.hip: second turns, and the guards that pick another kernel
+
+needs_ref = pytest.mark.skipif(not helpers.have_ref(), reason="oracle/_ref not built")
+
+
+def gated_call(fn):
+    """-> (result, {gate: launches}) of fn()."""
+    lib = _ffi.lib
+    lib.vips_hip_gate_reset()
+    lib.vips_hip_gate_enable(1)
+    try:
+        got = fn()
+        report = {k: n for k, (n, _) in libvips_amd.gate_report().items()}
+    finally:
+        lib.vips_hip_gate_enable(0)
+        lib.vips_hip_gate_reset()
+    return got, report
+
+
+def same_bytes(got, want, what):
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, got.shape, want.dtype, want.shape)
+    assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), what
+
+
+def check_conv(src, mask, precision, gate, what):
+    mask = np.asarray(mask, np.float64)
+    scale, offset = 3.0, 2.0
+    want = Ref.run_mask("conv", src, mask, scale, offset, "precision=" + precision)
+    got, report = gated_call(lambda: Image.new_from_array(src).conv(mask, scale=scale, offset=offset, precision=precision).numpy())
+    assert report == {gate: 1}, (what, report)
+    same_bytes(got, want, what)
+
+
+RAND3 = [[1.0, -2.0, 3.0], [4.0, 5.0, -1.0], [-3.0, 2.0, 1.0]]
+
+
+@needs_ref
+@pytest.mark.parametrize("precision", ["integer", "float"])
+def test_conv_general_second_turn(precision):
+    """A mask of two elements goes to the one-element-a-lane kernel whatever the size: three more rows than it has in
+    flight, int images (the narrow formats have kernels of their own), three pels wide."""
+    lib = _ffi.lib
+    rows = lib.vips_hip_conv_step(1) + 3
+    assert rows > lib.vips_hip_conv_step(1) > 0
+    src = helpers.lcg_image(3, rows, 2, np.int32, 171) // 65536
+    check_conv(src, [[2.0, -3.0]], precision, "convi" if precision == "integer" else "convf", ("1x2", precision, rows))
+
+
+@needs_ref
+@pytest.mark.parametrize("side", ["at", "over"])
+@pytest.mark.parametrize("case", ["tiled-integer", "tiled-float", "grouped-float"])
+def test_conv_tall_image_guards_second_turn(case, side):
+    """The register-tiled kernels (3 x 3, both precisions) and the grouped float kernel (a dense mask eight wide on an
+    integer image) put a row of blocks a row in grid.y: outputs of exactly the most rows a grid takes run on them, one
+    row more goes to the one-element-a-lane kernel, which then takes its rows in three turns.  The same bytes as the
+    reference on both sides; the gate is the precision's on both."""
+    lib = _ffi.lib
+    limit = lib.vips_hip_conv_step(2)
+    rows = limit + (side == "over")
+    assert limit > lib.vips_hip_conv_step(1) > 0 and (rows > limit) == (side == "over")
+    src = helpers.lcg_image(9 if case == "grouped-float" else 3, rows, 1, np.int32, 173) // 65536
+    if case == "grouped-float":
+        mask = [[1.0, 2.0, -1.0, 3.0, 1.5, -2.0, 1.0, 4.0], [2.0, 1.0, 1.0, -1.0, 0.5, 2.0, -3.0, 1.0]]
+    else:
+        mask = RAND3
+    precision = "integer" if case == "tiled-integer" else "float"
+    check_conv(src, mask, precision, "convi" if precision == "integer" else "convf", (case, side, rows))
+
+
+@needs_ref
+@pytest.mark.parametrize("case", [("conva", np.uint8), ("conva", np.float32), ("convasep", np.uint16), ("convasep", np.float32)],
+                         ids=lambda c: "%s-%s" % (c[0], np.dtype(c[1]).name))
+def test_approximate_second_turn(case, monkeypatch):
+    """The box-sum kernels (conva, convasep on integers, convasep on floats) with three more rows than grid.y takes:
+    float pels are k + j / 256, whose sums are exact."""
+    monkeypatch.setenv("VIPS_HIP_NO_APPROX_FAST", "1")
+    lib = _ffi.lib
+    op, dtype = case
+    rows = lib.vips_hip_conva_step(1) + 3
+    assert rows > lib.vips_hip_conva_step(1) > 0
+    src = helpers.lcg_image(4, rows, 2, np.uint16, 175)
+    src = (src.astype(np.float32) / np.float32(256)) if dtype == np.float32 else (src >> 8).astype(dtype) if dtype == np.uint8 else src
+    if op == "conva":
+        mask = np.array([[1.0, 2.0, 1.0], [2.0, 8.0, 2.0], [1.0, 2.0, 1.0]])
+        want = Ref.run_mask("conva", src, mask, 20.0, 1.0, "layers=5,cluster=1")
+        got, report = gated_call(lambda: Image.new_from_array(src).conva(mask, 20.0, 1.0, 5, 1).numpy())
+    else:
+        mask = np.array([[1.0, 3.0, 7.0, 3.0, 1.0]])
+        want = Ref.run_mask("convasep", src, mask, 15.0, 1.0, "layers=5")
+        got, report = gated_call(lambda: Image.new_from_array(src).convasep(mask.reshape(-1), 15.0, 1.0, 5).numpy())
+    assert set(report) == {op} and report[op] in (1, 2), report  # (convasep: a pass an axis)
+    same_bytes(got, want, (op, np.dtype(dtype).name, rows))

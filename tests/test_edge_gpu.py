@@ -421,6 +421,48 @@ def test_compass_general_formats(dtype):
     check_compass(src, LOP3, 2, "d180", "max", "integer")
 
 
+def tall(width, bands, dtype, seed):
+    """Four more rows than the combining kernels have in flight, a few pels wide: noise."""
+    rows = lib.vips_hip_edge_step(6) + 4
+    assert rows > lib.vips_hip_edge_step(6) > 0
+    return np.ascontiguousarray(helpers.lcg_image(width, rows, bands, dtype, seed))
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.int16, np.float32], ids=lambda d: np.dtype(d).name)
+def test_edge_combine_second_turn(dtype):
+    """More rows than grid.y of edge_combine_f32 (short and float images, against the reference) and of edge_combine_u8:
+    a block's second row.  edge_combine_u8 runs for uchar under the Highway arithmetic, which the scalar reference does
+    not have: as in test_uchar_general_tier its result is compared with the library's own two convolutions under that
+    arithmetic combined in numpy (edge.c:96-104), so this case checks the combine, not the convolutions; the fused
+    kernel on the same tall image is then compared with the reference."""
+    src = tall(3, 1, dtype, 131)
+    if dtype != np.uint8:
+        check_edge(src, "sobel", "second turn")
+        return
+    want = Ref.run("sobel", src)
+    lib.vips_hip_vector_set_enabled(1)
+    try:
+        im = Image.new_from_array(src)
+        with gated() as g:
+            got = im.sobel().numpy()
+        c1 = im.conv(np.array([[1.0, 2.0, 1.0], [0.0, 0.0, 0.0], [-1.0, -2.0, -1.0]]), scale=2.0, offset=128.0, precision="integer").numpy()
+        c2 = im.conv(np.array([[-1.0, 0.0, 1.0], [-2.0, 0.0, 2.0], [-1.0, 0.0, 1.0]]), scale=2.0, offset=128.0, precision="integer").numpy()
+    finally:
+        lib.vips_hip_vector_set_enabled(0)
+    ran, convs = families(g.report)
+    assert ran == {"edge_combine_u8": 1} and convs == 2, g.report
+    same(got, uchar_combine(c1, c2), "general tier on uchar, second turn")
+    # (the reference's own C path rounds a negative sum another way: where no sum is negative before the offset the
+    # two agree, and everywhere the fused kernel is the reference)
+    same(run_edge(src, "sobel"), want, "fused, tall")
+
+
+@pytest.mark.parametrize("combine", COMBINES)
+def test_compass_combine_second_turn(combine):
+    """More rows than grid.y of compass_combine: a block's second row."""
+    check_compass(tall(4, 2, np.int16, 133), LOP3, 3, "d45", combine, "float")
+
+
 def test_compass_defaults_and_errors():
     src = noise(60, 30, 3, np.uint8, 121)
     want = Ref.run_mask("compass", src, KIRSCH)

@@ -11,8 +11,8 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 NAME = "test_arith_file_on_the_cpu"
 # test -> (files, -k deselections, at least this many cases must pass): 6 + 2 + 12 linear on domains, 1 errors and
 # operators, 16 + 1 invert / abs, 60 + 8 + 20 sweeps, 1 models, 4 + 1 whole images, 8 + 4 + 24 + 4 + 7 two images, 50 + 4 + 1 + 2 + 2 + 2 + 1 stats (the
-# 3 module cases need the module's own library)
-suite.JOBS[NAME] = (["tests/test_arith_gpu.py"], [], 241)
+# 3 module cases need the module's own library), 3 + 3 second turns of the capped grids
+suite.JOBS[NAME] = (["tests/test_arith_gpu.py"], [], 247)
 
 
 def test_arith_file_on_the_cpu():

@@ -13,12 +13,13 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 # 12 round + 1, 16 sign, 16 clamp, 32 + 3 + 1 pairs, 16 + 16 + 1 remainder, 1 refusals, 3 region forms
 ARITH2 = "test_arith2_file_on_the_cpu"
 suite.JOBS[ARITH2] = (["tests/test_arith2_gpu.py"], [], 118)
-# 18 stream shapes, 3 forced, 4 general shapes, 8 formats, 2 order, 1 extremes, 4 matrix images, 1 refusals, 3 region forms
+# 18 stream shapes, 3 forced, 4 general shapes, 8 formats, 2 order, 1 extremes, 4 matrix images, 1 refusals, 3 region forms,
+# 2 + 2 + 3 second turns of the capped grids
 RECOMB = "test_recomb_file_on_the_cpu"
-suite.JOBS[RECOMB] = (["tests/test_recomb_gpu.py"], [], 44)
-# 8 + 16 + 2 + 1 sum, 10 + 12 + 16 + 2 + 1 bandrank, 1 seventeen
+suite.JOBS[RECOMB] = (["tests/test_recomb_gpu.py"], [], 51)
+# 8 + 16 + 2 + 1 sum, 10 + 12 + 16 + 2 + 1 bandrank, 1 seventeen, 2 + 4 + 2 + 2 second turns of the capped grids
 NARY = "test_nary_file_on_the_cpu"
-suite.JOBS[NARY] = (["tests/test_nary_gpu.py"], [], 69)
+suite.JOBS[NARY] = (["tests/test_nary_gpu.py"], [], 79)
 
 
 def test_arith2_file_on_the_cpu():

@@ -11,8 +11,8 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 NAME = "test_cells_file_on_the_cpu"
 # test -> (files, -k deselections, at least this many cases must pass): 4 + 1 model, 1 anchors, 20 + 2 + 2 sweep, 20 + 2
 # replicate, 2 clamp, 2 cropping, 2 + 1 against the reference, 1 zoom / subsample, 2 + 2 regions, 1 refusals (the
-# module's three need the module's own library, the two-device case two devices)
-suite.JOBS[NAME] = (["tests/test_cells_gpu.py"], [], 65)
+# module's three need the module's own library, the two-device case two devices), 2 + 5 + 4 second turns of the capped grids
+suite.JOBS[NAME] = (["tests/test_cells_gpu.py"], [], 76)
 
 
 def test_cells_file_on_the_cpu():

@@ -11,8 +11,8 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 NAME = "test_edge_file_on_the_cpu"
 # test -> (files, -k deselections, at least this many cases must pass): 19 of sobel / scharr / prewitt, 3 + 3 + 1 + 3 +
 # 5 + 1 + 3 of compass, 3 + 3 + 2 + 4 + 1 + 1 of canny, 4 of the region forms' and refusals' rest (the module's three
-# need the module's own library)
-suite.JOBS[NAME] = (["tests/test_edge_gpu.py"], [], 60)
+# need the module's own library), 3 + 3 second turns of the combining kernels
+suite.JOBS[NAME] = (["tests/test_edge_gpu.py"], [], 66)
 
 
 def test_edge_file_on_the_cpu():

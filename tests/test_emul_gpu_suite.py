@@ -23,10 +23,10 @@ pytestmark = pytest.mark.skipif(not ENABLED,
 # test -> (files, -k deselections, at least this many cases must pass).  Independent child processes of minutes
 # each: conftest.py starts the selected ones when collection ends (prestart), the test waits for its own.
 JOBS = {
-    "test_conv_colour_file_on_the_cpu": (["tests/test_conv_colour_gpu.py"], [], 589),
+    "test_conv_colour_file_on_the_cpu": (["tests/test_conv_colour_gpu.py"], [], 601),
     "test_c1_and_the_new_kernels_files_on_the_cpu": (["tests/test_c1_vipsthumbnail.py", "tests/test_convsep_int_gpu.py"], [], 38),
     "test_resample_file_on_the_cpu": (["tests/test_resample_gpu.py"],
-                                      ["resize", "thumbnail", "c2_full", "c2_quarter", "mfma_variants", "region_windows", "any_bands"], 160),
+                                      ["resize", "thumbnail", "c2_full", "c2_quarter", "mfma_variants", "region_windows", "any_bands"], 163),
     "test_dispatch_fuzz_file_on_the_cpu": (["tests/test_fuzz_dispatch_gpu.py"], [], 6),
     "test_colour_routes_file_on_the_cpu": (["tests/test_colour_routes_gpu.py"], [], 176),
 }

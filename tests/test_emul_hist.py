@@ -11,8 +11,8 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 NAME = "test_hist_file_on_the_cpu"
 # test -> (files, -k deselections, at least this many cases must pass): 3 + 1 of hist_cum / hist_norm, 3 + 1 of
 # hist_equal, 8 + 3 + 1 + 1 + 1 of maplut, 10 + 1 + 3 + 3 + 1 of hist_local, 7 + 3 + 1 + 1 + 1 of stdif, 4 + 3 region
-# cases (the module's three need the module's own library)
-suite.JOBS[NAME] = (["tests/test_hist_gpu.py"], [], 60)
+# cases (the module's three need the module's own library), 2 second turns of maplut, 1 tall-image guard of stdif
+suite.JOBS[NAME] = (["tests/test_hist_gpu.py"], [], 63)
 
 
 def test_hist_file_on_the_cpu():

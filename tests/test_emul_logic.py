@@ -11,8 +11,8 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 NAME = "test_logic_file_on_the_cpu"
 # test -> (files, -k deselections, at least this many cases must pass): the 643 cases of the file that need no module library, as observed (12 + 42 + 48 +
 # 1 relational, 10 + 35 + 40 + 1 boolean, 6 + 1 matching, 16 + 1 + 1 ifthenelse, 1 + 8 + 8 + 1 bands, 360 + 8 + 40 + 1 sweeps, 2 errors
-# and operators)
-suite.JOBS[NAME] = (["tests/test_logic_gpu.py"], [], 643)
+# and operators), 3 + 6 second turns of the capped grids
+suite.JOBS[NAME] = (["tests/test_logic_gpu.py"], [], 652)
 
 
 def test_logic_file_on_the_cpu():

@@ -10,8 +10,8 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 
 NAME = "test_mapim_file_on_the_cpu"
 # test -> (files, -k deselections, at least this many cases must pass): 180 + 1 of the coordinate stage, 35 image formats,
-# 8 alpha, 4 index sizes, 3 scattered, 3 + 1 + 4 region cases, 2 errors, 1 refusals, 3 xyz, 1 pipeline
-suite.JOBS[NAME] = (["tests/test_mapim_gpu.py"], [], 246)
+# 8 alpha, 4 index sizes, 3 scattered, 3 + 1 + 4 region cases, 2 errors, 1 refusals, 3 xyz, 1 pipeline, 2 + 1 second turns
+suite.JOBS[NAME] = (["tests/test_mapim_gpu.py"], [], 249)
 
 
 def test_mapim_file_on_the_cpu():

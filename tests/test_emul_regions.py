@@ -9,9 +9,9 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
                                 reason="a real GPU is present, or the reference / mock runtime / emulation cannot be built")
 
 NAME = "test_regions_file_on_the_cpu"
-# test -> (files, -k deselections, at least this many cases must pass): the 51 cases of the file (4 + 1 + 2 + 1 + 4 + 15 + 5
-# + 1 + 1 + 1 labelregions, 1 + 5 + 8 + 1 countlines, 1 of refusals)
-suite.JOBS[NAME] = (["tests/test_regions_gpu.py"], [], 51)
+# test -> (files, -k deselections, at least this many cases must pass): the 52 cases of the file (4 + 1 + 2 + 1 + 4 + 15 + 5
+# + 1 + 1 + 1 labelregions, 1 + 5 + 8 + 1 + 1 countlines, 1 of refusals)
+suite.JOBS[NAME] = (["tests/test_regions_gpu.py"], [], 52)
 
 
 def test_regions_file_on_the_cpu():

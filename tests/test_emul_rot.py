@@ -11,8 +11,8 @@ pytestmark = pytest.mark.skipif(not suite.ENABLED,
 NAME = "test_rot_file_on_the_cpu"
 # test -> (files, -k deselections, at least this many cases must pass): 96 kernel cases, 8 double, 12 behind the
 # switch, 8 many-tile, 1 orientation, 2 anchors, 5 region views, 32 + 1 + 4 thumbnails, the .v round trip; the two
-# JPEG cases need Pillow and a reference with libjpeg
-suite.JOBS[NAME] = (["tests/test_rot_gpu.py"], [], 170)
+# JPEG cases need Pillow and a reference with libjpeg; 6 + 5 second turns of the capped grids
+suite.JOBS[NAME] = (["tests/test_rot_gpu.py"], [], 181)
 
 
 def test_rot_file_on_the_cpu():

@@ -238,6 +238,21 @@ def test_maplut_row_widths(dtype):
     same(run_maplut(src, column), model_maplut(src, lut), "column LUT")
 
 
+@pytest.mark.parametrize("form", [(3, 3, -1), (1, 4, -1)], ids=lambda f: "%dthrough%d" % f[:2])
+def test_maplut_second_turn(tmp_path, form):
+    """More rows than the launch has waves (a wave takes a row at a time), rows of 21 and 7 bytes that start on every
+    byte of a dword."""
+    ib, lb, band = form
+    rows_of_a_step = lib.vips_hip_hist_step(3) * lib.vips_hip_hist_step(1)
+    src = np.ascontiguousarray(helpers.lcg_image(7, rows_of_a_step + 7, ib, np.uint8, 91 + ib))
+    assert src.shape[0] > rows_of_a_step
+    lut = make_lut(256, lb, np.uint16, 93 + lb)
+    path = str(tmp_path / "lut.v")
+    helpers.write_v(path, lut, interpretation=HISTOGRAM)
+    want = Ref.run("maplut", src, "lut=" + path)
+    same(run_maplut(src, lut, band), want, "maplut second turn %r" % (form,))
+
+
 def test_the_maplut_model_is_the_reference(tmp_path):
     """vips_object_set_from_string loads an image argument from a file name: the LUT goes over as a .v file."""
     cases = [(3, 1, -1, np.uint8, 256), (1, 3, -1, np.uint16, 256), (3, 3, -1, np.float32, 10), (3, 1, 1, np.int16, 10),
@@ -505,6 +520,21 @@ def test_stdif_largest_windows():
          "model 15x17")
     same(run_stdif(src, 257, 257), model_stdif(src, 257, 257), "stdif 257x257")
     same(run_stdif(src, 257, 257, a=1.0, b=2.0, s0=1.0), model_stdif(src, 257, 257, a=1.0, b=2.0, s0=1.0), "stdif 257x257")
+
+
+def test_stdif_tall_image_guard_second_turn():
+    """An 87 x 256 window on four bands leaves room in LDS for one output row a block, so a row of blocks is a row of
+    the image and the grid takes 65 535 of them: one row more is refused by name, before any launch.  (The side that
+    runs is not here: 131 070 blocks that each stage 256 rows of 608 bytes, and a reference of 22 M elements under a
+    window of 22 272 pels, are no test of seconds; windows that leave two rows a block put the guard at 131 070 rows.)"""
+    src = np.ascontiguousarray(helpers.lcg_image(87, 65536, 4, np.uint8, 181))
+    with gated() as g:
+        with pytest.raises(VipsHipError, match="stdif: image too large"):
+            Image.new_from_array(src).stdif(87, 256)
+    assert g.ran == {}, g.ran
+    # two rows fewer in the window and a block makes two rows: the same image runs into no guard
+    small = np.ascontiguousarray(src[:300])
+    same(run_stdif(small, 87, 250), Ref.run("stdif", small, sd_args(87, 250)), "stdif 87x250")
 
 
 def test_stdif_errors_and_refusals():

@@ -690,6 +690,57 @@ def test_grid_stride():
     same(got, model_select(c1, a, b), "select")
 
 
+@pytest.mark.parametrize("nick", ["relational_const", "bandmean", "extract_band"])
+def test_second_turn_of_the_streams_in_frames(nick):
+    """Rows that stay rows: a window of a larger frame whose rows together have more units than the capped grid has
+    lanes, so that a lane's second unit is on another row and elsewhere in it (for the constants: at another phase of
+    the band vector); every row ends in a ragged unit, and nothing outside the window is written (gen_in_frames).
+    Units: 16 bytes of output for logic_stream (relational_const) and logic_band_stream (bandmean), 16 pels of uchar
+    for logic_band_pels (extract_band).  (ifthenelse has no region form -- vips_hip_ifthenelse takes whole images, whose
+    rows are always joined -- so logic_select_stream cannot be given rows that stay rows; test_grid_stride turns it on
+    a whole image.)"""
+    lanes = lib.vips_hip_logic_step(2) * lib.vips_hip_logic_step(0)
+    group = lib.vips_hip_logic_step(1)
+    width = (4096 + 5) // 3 if nick == "relational_const" else 4096 + 5  # 4101 output elements a row
+    out_elems = width * 3 if nick == "relational_const" else width
+    units = -(-out_elems // group)
+    height = lanes // units + 9
+    assert out_elems % group and height > 1 and units * height > lanes and lanes % units and lanes % units * group % 3
+    src = noise(width, height, np.uint8, 3, 431)
+    args, call, out_dtype, out_bands = gen_case(nick, src)
+    with gated() as g:
+        got = gen_in_frames(src, out_dtype, out_bands, call, 4)
+    assert g.ran == {{"relational_const": "logic_stream", "bandmean": "logic_band_stream", "extract_band": "logic_band_pels"}[nick]: 1}, g.ran
+    same(got, Ref.run(nick, src, args), nick)
+
+
+@pytest.mark.parametrize("blocks", [1, 3])
+@pytest.mark.parametrize("nick", ["relational_const", "bandmean", "ifthenelse"])
+def test_second_turn_of_the_general_kernels(nick, blocks):
+    """The one-element-a-lane kernels with more rows than grid.y, which is the cap for rows of one block and a third of
+    it for rows of three (the last ragged)."""
+    threads, cap = lib.vips_hip_logic_step(0), lib.vips_hip_logic_step(2)
+    out_elems = (blocks - 1) * threads + 63
+    width = out_elems if nick == "bandmean" else out_elems // 3
+    out_elems = width if nick == "bandmean" else width * 3
+    in_flight = -(-cap // blocks)
+    rows = in_flight + (3 if blocks == 1 else 2)
+    assert -(-out_elems // threads) == blocks and out_elems % threads and rows > in_flight and (blocks == 1) == (in_flight == cap)
+    src = noise(width, rows, np.int16, 3, 441)
+    if nick == "ifthenelse":
+        other, cond = noise(width, rows, np.int16, 3, 443), noise(width, rows, np.uint8, 1, 445) & 0x81
+        with general_kernel(), gated() as g:
+            got = Image.new_from_array(cond).ifthenelse(Image.new_from_array(src), Image.new_from_array(other)).numpy()
+        assert g.ran == {"logic_select_general": 1}, g.ran
+        same(got, model_select(cond, src, other), (nick, blocks))
+        return
+    args, call, out_dtype, out_bands = gen_case(nick, src)
+    with general_kernel(), gated() as g:
+        got = gen_in_frames(src, out_dtype, out_bands, call, 4)
+    assert g.ran == {GEN_KERNELS[nick] + "general": 1}, g.ran
+    same(got, Ref.run(nick, src, args), (nick, blocks))
+
+
 # ---------------------------------------------------------------- errors, operators, refusals
 
 def test_errors_are_the_references(tmp_path):

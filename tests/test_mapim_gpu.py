@@ -394,6 +394,78 @@ def test_region_form_index_rows_off_their_pels(dtype, margin, extra):
     del idx_dev
 
 
+# ---- the capped grids' second turn
+
+def need_of_bounds(index, in_width, in_height, args):
+    """vips_hip_mapim_bounds_need (the host half, which the region tests pin) of numpy's extremes of the index."""
+    with np.errstate(invalid="ignore"):
+        lo, hi = np.nanmin(index.astype(np.float64), axis=(0, 1)), np.nanmax(index.astype(np.float64), axis=(0, 1))
+    bounds = (ctypes.c_double * 4)(lo[0], lo[1], hi[0], hi[1])
+    need = (ctypes.c_int * 4)()
+    _ffi.check(lib.vips_hip_mapim_bounds_need(bounds, ctypes.byref(args), in_width, in_height, need))
+    return list(need)
+
+
+@pytest.mark.parametrize("case", ["rows", "pels"])
+def test_bounds_second_turn(case):
+    """The bounds pass beyond its grid.  rows: an index one block wide with three more rows than grid.y; pels: an index
+    300 pels wider than the launch's lanes (its blocks of a row alone use up the launch, so grid.y is 1 and the second
+    row is a second turn too).  Every one of the four extremes is unique and lies where only a second turn reads -- for
+    pels: two past the first step of the pel loop, two in the second row -- each with a NaN beside it; the four clipped
+    integers, through the need they give, are those of numpy's extremes."""
+    threads, most, budget = lib.vips_hip_mapim_step(5), lib.vips_hip_mapim_step(4), lib.vips_hip_mapim_step(7)
+    if case == "rows":
+        width, height = 37, budget + 3
+        assert -(-width // threads) == 1 and height > budget
+        spots = [(budget, 5), (budget + 1, 30), (budget + 2, 0), (budget + 2, 36)]
+    else:
+        width, height = most * threads + 300, 2
+        blocks_x = -(-width // threads)
+        assert blocks_x > most and -(-budget // blocks_x) == 1 < height
+        spots = [(0, most * threads + 7), (0, width - 1), (1, 5), (1, most * threads + 100)]
+    rng = np.random.default_rng(181)
+    index = (5000.0 + 4000.0 * rng.random((height, width, 2))).astype(np.float32)
+    (ya, xa), (yb, xb), (yc, xc), (yd, xd) = spots
+    index[ya, xa, 0] = 1000.25   # the least x
+    index[yb, xb, 1] = 20000.75  # the greatest y
+    index[yc, xc, 1] = 2000.5    # the least y
+    index[yd, xd, 0] = 30000.5   # the greatest x
+    for y, x in spots:
+        index[y, x - 1 if x else x + 1, :] = np.nan
+    args = Image.mapim_args(interpolate="bilinear")
+    in_width = in_height = 1 << 20
+    want = need_of_bounds(index, in_width, in_height, args)
+    # (every extreme counts: without any one of them the need is another)
+    for y, x in spots:
+        less = index.copy()
+        less[y, x] = 6000.0
+        assert need_of_bounds(less, in_width, in_height, args) != want
+    index_im = Image.new_from_array(index)
+    r_index = index_im.region()
+    need = (ctypes.c_int * 4)()
+    with gated() as g:
+        _ffi.check(lib.vips_hip_mapim_need(ctypes.byref(r_index), ctypes.byref(args), in_width, in_height, need))
+    assert g.ran == {"mapim_bounds": 1} and g.others == {}, (g.ran, g.others)
+    assert list(need) == want, (list(need), want)
+
+
+def test_xyz_second_turn(tmp_path):
+    """More two-pel groups than an xyz launch has lanes, odd rows (their last group is one pel): the lanes' second group
+    is in another row, elsewhere in it."""
+    lanes = lib.vips_hip_mapim_step(7) * lib.vips_hip_mapim_step(5)
+    w = 1021
+    groups = (w + 1) // 2
+    h = lanes // groups + 9
+    assert w % 2 and groups * h > lanes and lanes % groups
+    o = str(tmp_path / "xyz.v")
+    run_vips(["xyz", o, str(w), str(h)])
+    want, _ = helpers.read_v(o)
+    with gated() as g:
+        got = Image.xyz(w, h).numpy()
+    same(got, want, "xyz %d x %d" % (w, h))
+    assert g.ran == {} and g.others == {"xyz": 1}, g.others
+
+
 # ---- errors and refusals
 
 def last_line(text):

@@ -222,6 +222,73 @@ def test_bandrank_matches_and_refuses(tmp_path):
             dev(op, [(z, 0), (z, 0)])
 
 
+# ---------------------------------------------------------------- the capped grid's second turn
+
+def lanes_of_a_step():
+    """Units a stream launch takes before a lane comes back for a second one."""
+    return lib.vips_hip_nary_step(1) * lib.vips_hip_nary_step(0)
+
+
+def side_over_the_grid(unit_elems, bands=BANDS):
+    """A square side whose image has 700 more units of `unit_elems` output elements than a capped grid takes in one
+    step, and a ragged last unit."""
+    elems = (lanes_of_a_step() + 700) * unit_elems + 3
+    side = int(np.sqrt(elems // bands)) + 1
+    while unit_elems > 1 and side * side * bands % unit_elems == 0:
+        side += 1
+    assert -(-side * side * bands // unit_elems) > lanes_of_a_step()
+    return side
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16], ids=name_of)
+def test_sum_second_turn_of_the_stream(tmp_path, dtype):
+    """A whole image (its rows joined) of more 16-byte groups of uint than the grid has lanes: the lanes' second unit,
+    the last one ragged."""
+    side = side_over_the_grid(lib.vips_hip_nary_step(2) // 4)
+    images = array_of(3, dtype, 801, shape=(side, side, BANDS))
+    assert check(tmp_path, "sum", images, "stream", ("second turn", name_of(dtype))).dtype == np.uint32
+
+
+@pytest.mark.parametrize("case", [(np.uint8, 1), (np.float64, 1), (np.uint8, 0), (np.int16, 2)], ids=lambda c: "%s-%d" % (name_of(c[0]), c[1]))
+def test_bandrank_second_turn_of_the_stream(tmp_path, case):
+    """Index 1 of 3 takes a dword (a double) a lane, index 0 and 2 (minimum, maximum) 16 bytes: each over the grid."""
+    dtype, index = case
+    group = lib.vips_hip_nary_step(2) if index != 1 else lib.vips_hip_nary_step(4 if dtype == np.float64 else 3)
+    side = side_over_the_grid(max(1, group // np.dtype(dtype).itemsize))
+    images = array_of(3, dtype, 811, shape=(side, side, BANDS))
+    check(tmp_path, "bandrank", images, "stream", ("second turn", name_of(dtype)), index=index)
+
+
+def rows_over_the_grid(elems, extra):
+    """`extra` more rows than the one-element-a-lane kernel has in flight for rows of `elems` elements."""
+    blocks_x = -(-elems // lib.vips_hip_nary_step(0))
+    in_flight = -(-lib.vips_hip_nary_step(1) // blocks_x)
+    return blocks_x, in_flight, in_flight + extra
+
+
+@pytest.mark.parametrize("op", ["sum", "bandrank"])
+def test_second_turn_of_the_general_kernel_one_block_a_row(tmp_path, op):
+    """Rows of one block, three more of them than grid.y: the blocks' second row."""
+    blocks_x, in_flight, rows = rows_over_the_grid(W * BANDS, 3)
+    assert blocks_x == 1 and rows > in_flight
+    images = array_of(3, np.uint8 if op == "sum" else np.float32, 821, shape=(W, rows, BANDS))
+    check(tmp_path, op, images, "general", ("second turn", rows), index=None if op == "sum" else 1)
+
+
+@pytest.mark.parametrize("op", ["sum", "bandrank"])
+def test_second_turn_of_the_general_kernel_three_blocks_a_row(tmp_path, op):
+    """Rows of three blocks, the last ragged, two more rows than grid.y (which is not the cap itself here).  The second
+    image ends one row into the second turn and the third is narrower: zero outside their own rectangles there too."""
+    width = 2 * lib.vips_hip_nary_step(0) // BANDS + 30
+    blocks_x, in_flight, rows = rows_over_the_grid(width * BANDS, 2)
+    assert blocks_x == 3 and in_flight < lib.vips_hip_nary_step(1) and rows > in_flight and width * BANDS % lib.vips_hip_nary_step(0)
+    sizes = [(width, rows), (width, in_flight + 1), (width - 50, rows)]
+    images = [(noise(w, h, np.int16, BANDS, 831 + i), INTERP["srgb"]) for i, (w, h) in enumerate(sizes)]
+    # (no switch: images of different sizes are the general kernel's as dispatched)
+    got = check(tmp_path, op, images, "as dispatched", ("second turn", sizes), index=None if op == "sum" else 0, ran="general")
+    assert got.shape == (rows, width, BANDS)
+
+
 def test_seventeen_images_are_refused_by_name():
     images = [(noise(5, 4, np.uint8, 1, 781 + i), INTERP["b-w"]) for i in range(17)]
     for op in ("sum", "bandrank"):

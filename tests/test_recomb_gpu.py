@@ -219,6 +219,68 @@ def test_refusals(tmp_path):
         im.recomb(Image.new_from_array(z[:3, :3, :1]))
 
 
+# ---------------------------------------------------------------- the capped grid's second turn
+
+def lanes_of_a_step():
+    """Runs a stream launch takes before a lane comes back for a second one."""
+    return lib.vips_hip_recomb_step(1) * lib.vips_hip_recomb_step(0)
+
+
+def rows_over_the_grid(width, extra):
+    """`extra` more rows than the one-pel-a-lane kernel has in flight for rows of `width` pels."""
+    blocks_x = -(-width // lib.vips_hip_recomb_step(0))
+    in_flight = -(-lib.vips_hip_recomb_step(1) // blocks_x)
+    return blocks_x, in_flight, in_flight + extra
+
+
+@pytest.mark.parametrize("shape", [(3, 1), (3, 3)], ids=lambda s: "%dto%d" % s)
+def test_second_turn_of_the_stream_on_a_whole_image(tmp_path, shape):
+    """A whole uchar image (its rows joined) of more runs -- of at most vips_hip_recomb_step(2) pels -- than the grid has
+    lanes, the last run ragged: 12 bytes in, one and three 16-byte groups out a run."""
+    mw, mh = shape
+    run = lib.vips_hip_recomb_step(2)
+    side = int(np.sqrt((lanes_of_a_step() + 700) * run + 3)) + 1
+    while side * side % run == 0:
+        side += 1
+    assert side * side // run > lanes_of_a_step()
+    src = noise(side, side, np.uint8, mw, 271, with_extremes=True)
+    check(tmp_path, src, matrix_of(mw, mh, 273), "stream", ("second turn", shape, side), interp=INTERP["srgb"])
+
+
+@pytest.mark.parametrize("case", [(np.uint8, (3, 1)), (np.uint16, (3, 3))], ids=lambda c: "%s-%dto%d" % ((name_of(c[0]),) + c[1]))
+def test_second_turn_of_the_stream_in_frames(tmp_path, case):
+    """Rows that stay rows: a window of a larger frame whose rows together have more runs than the grid has lanes, so
+    that the second turn splits its position into a row and a run of it; every row ends in a ragged run, and nothing
+    outside the window is written."""
+    dtype, (mw, mh) = case
+    run = lib.vips_hip_recomb_step(2)
+    width = 4096 // (4 * mh) + 1
+    runs = -(-width // run)
+    height = lanes_of_a_step() // runs + 9
+    # (at least ceil(width / most pels of a run) runs a row; the second turn starts inside a row)
+    assert width % run and height > 1 and runs * height > lanes_of_a_step() and lanes_of_a_step() % runs
+    m = np.ascontiguousarray(matrix_of(mw, mh, 281))
+    src = noise(width, height, dtype, mw, 283, with_extremes=True)
+    want, _ = ref_recomb(tmp_path, src, m)
+    with gated() as g:
+        got = gen_in_frames(src, np.float32, mh, lambda i, o: lib.vips_hip_recomb_gen(m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), mw, mh, i, o), 4)
+    assert g.ran == {"recomb_stream": 1}, g.ran
+    same_bits(got, want, ("second turn in frames", name_of(dtype), mw, mh))
+
+
+@pytest.mark.parametrize("case", [(np.uint8, (3, 3), 1, 3), (np.int16, (2, 5), 3, 2), (np.float64, (4, 1), 3, 2)],
+                         ids=lambda c: "%s-%dto%d-%dblocks" % ((name_of(c[0]),) + c[1] + (c[2],)))
+def test_second_turn_of_the_general_kernel(tmp_path, case):
+    """The one-pel-a-lane kernel with more rows than grid.y: rows of one block (grid.y is the cap) and rows of three
+    blocks, the last ragged (grid.y is a third of it)."""
+    dtype, (mw, mh), blocks, extra = case
+    width = (blocks - 1) * lib.vips_hip_recomb_step(0) + 41
+    blocks_x, in_flight, rows = rows_over_the_grid(width, extra)
+    assert blocks_x == blocks and rows > in_flight and (blocks == 1) == (in_flight == lib.vips_hip_recomb_step(1))
+    src = noise(width, rows, dtype, mw, 291, with_extremes=True, finite=True)
+    check(tmp_path, src, matrix_of(mw, mh, 293), "general", ("second turn", name_of(dtype), width, rows), force_general=True)
+
+
 # ---------------------------------------------------------------- the region form
 
 @pytest.mark.parametrize("kernel", ["stream", "general", "unaligned"])

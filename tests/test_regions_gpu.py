@@ -202,6 +202,20 @@ def test_countlines_formats(tmp_path, dtype):
             check_lines(tmp_path, levels[pick].astype(dtype), bands)
 
 
+def test_countlines_second_turn(tmp_path):
+    """More strips than a launch has in flight: rows of a little over 65 536 uchar elements (257 blocks, the last
+    ragged, so seven strips in flight) and nine strips, the last ragged.  On the second turn a strip's first row looks
+    at the row above it, which another block's first turn owned: noise, so a rise lost or counted twice there moves the
+    count, in both directions."""
+    threads, strip, most = (lib.vips_hip_countlines_step(i) for i in range(3))
+    width = 256 * threads + 17
+    blocks_x = -(-width // threads)
+    in_flight = most // blocks_x
+    height = (in_flight + 2) * strip - 5
+    assert width % threads and in_flight >= 1 and -(-height // strip) > in_flight and height % strip
+    check_lines(tmp_path, helpers.lcg_image(width, height, 1, np.uint8, 61), (width, height))
+
+
 def test_countlines_constant(tmp_path):
     src = np.full((9, 70, 3), 200, np.uint8)
     check_lines(tmp_path, src)

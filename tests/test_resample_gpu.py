@@ -461,6 +461,33 @@ def test_resize_upsizing_vs_port(dtype, kernel):
             assert np.array_equal(got, want), (kernel, w, h, hs, vs)
 
 
+@pytest.mark.parametrize("case", [("linear", np.uint16, 1), ("cubic", np.float32, 3), ("nearest", np.uint8, 3)],
+                         ids=lambda c: "%s-%s-%dblocks" % (c[0], np.dtype(c[1]).name, c[2]))
+def test_upsize_second_turn(case):
+    """Narrow and tall: more output rows than an upsize launch has in flight -- its block budget over the blocks of a row,
+    rounded down -- for rows of one block and of three (the last ragged); bit-exact against the port."""
+    kernel, dtype, blocks = case
+    lib = _ffi.lib
+    threads, budget = lib.vips_hip_upsize_step(0), lib.vips_hip_upsize_step(1)
+    in_flight = budget // blocks
+    hs, vs = 2.3, 2.0
+    w, h = int(((blocks - 1) * threads + 40) / hs), in_flight // 2 + 6
+    src = helpers.lcg_image(w, h, 2, dtype, 79)
+    lib.vips_hip_gate_reset()
+    lib.vips_hip_gate_enable(1)
+    try:
+        got = Image.new_from_array(src).resize(hs, vscale=vs, kernel=kernel).numpy()
+        report = {k: n for k, (n, _) in libvips_amd.gate_report().items()}
+    finally:
+        lib.vips_hip_gate_enable(0)
+        lib.vips_hip_gate_reset()
+    assert -(-got.shape[1] // threads) == blocks and got.shape[1] % threads and got.shape[0] > in_flight, got.shape
+    assert report == {"upsize": 1}, report
+    want = Port.resize(src, hs, vs, kernel=kernel)
+    assert got.shape == want.shape
+    assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), case
+
+
 def test_upsize_region_rects_and_reference():
     """vips_hip_upsize_gen on output sub-rects with an input window that just covers them
     (a strip owner's call), and a 2048-wide enlargement against the compiled reference."""

@@ -170,6 +170,59 @@ def test_many_tiles(orientation):
         assert sorted(g.report) == sorted(stream_gates(1031, 3, orientation)), g.report
 
 
+def rows_over_the_grid(blocks_x, extra):
+    """`extra` more rows than a launch of blocks_x blocks a row has in flight."""
+    in_flight = -(-lib.vips_hip_rot_step(1) // blocks_x)
+    return in_flight, in_flight + extra
+
+
+@pytest.mark.parametrize("op", ["d180", "vertical", "horizontal"])
+@pytest.mark.parametrize("blocks", [1, 3])
+def test_flip_stream_second_turn(op, blocks):
+    """More rows than grid.y (the cap for rows of one block, a third of it for rows of three): a block's second row,
+    whose source row with d180 and vertical is height - 1 - y.  One block: RGB uchar, 48-byte groups; three: RGBA
+    uchar, 16-byte groups.  Rows end in a ragged group, which the one-pel-a-lane kernel takes -- on its second turn too."""
+    threads = lib.vips_hip_rot_step(0)
+    bands = 3 if blocks == 1 else 4
+    group = lib.vips_hip_rot_group(1 if op == "vertical" else bands)  # (a row-permuted copy moves rows of bytes)
+    assert group == (48 if bands == 3 and op != "vertical" else 16)
+    # whole groups for two lanes of the last block, or a few more, then 12 bytes: whole pels, three or four
+    chunks = (blocks - 1) * threads + 2
+    while (chunks * group + 12) % bands:
+        chunks += 1
+    width = (chunks * group + 12) // bands
+    in_flight, rows = rows_over_the_grid(blocks, 5 - blocks)
+    assert -(-chunks // threads) == blocks and width * bands % group == 12 and rows > in_flight
+    assert (blocks == 1) == (in_flight == lib.vips_hip_rot_step(1))
+    src = helpers.lcg_image(width, rows, bands, np.uint8, 31 + blocks)
+    with gated() as g:
+        got = run_op(Image.new_from_array(src), op).numpy()
+    want = expected(src, op)
+    assert got.shape == want.shape and np.array_equal(got, want)
+    assert {k: n for k, (n, _) in g.report.items()} == {"flip_stream": 1, "rot_general": 1}, g.report
+
+
+@pytest.mark.parametrize("case", [(np.uint8, 3, "d90", 1), (np.uint16, 1, "d270", 3), (np.float32, 1, "d180", 1), (np.float64, 1, "d90", 3),
+                                  (np.uint16, 4, "horizontal", 3)], ids=lambda c: "%s_x%d-%s-%dblocks" % ((np.dtype(c[0]).name,) + c[1:]))
+def test_rot_general_second_turn(case, monkeypatch):
+    """The one-pel-a-lane kernel with more output rows than grid.y, copying units of 1, 2, 4 and 8 bytes (odd widths
+    keep the rows' starts from allowing more than the element).  For the quarter turns the output's rows are the input's
+    width."""
+    monkeypatch.setenv("VIPS_HIP_NO_ROT_TILE", "1")
+    monkeypatch.setenv("VIPS_HIP_NO_FLIP_STREAM", "1")
+    dtype, bands, op, blocks = case
+    out_width = (blocks - 1) * lib.vips_hip_rot_step(0) + 41
+    in_flight, out_rows = rows_over_the_grid(blocks, 5 - blocks)
+    assert -(-out_width // lib.vips_hip_rot_step(0)) == blocks and out_rows > in_flight and out_width % 2
+    w, h = (out_rows, out_width) if transposes(op) else (out_width, out_rows)
+    src = helpers.lcg_image(w, h, bands, dtype, 37 + blocks)
+    with gated() as g:
+        got = run_op(Image.new_from_array(src), op).numpy()
+    want = expected(src, op)
+    assert got.shape == want.shape == (out_rows, out_width, bands) and np.array_equal(got, want)
+    assert {k: n for k, (n, _) in g.report.items()} == {"rot_general": 1}, g.report
+
+
 def test_rot_and_flip_keep_the_orientation_other_operations_drop_it():
     src = helpers.lcg_image(40, 30, 3, np.uint8, 1)
     im = Image.new_from_array(src)

@@ -178,6 +178,49 @@ def test_rectangles_against_bincount():
         im.hist_rects([(0, 0, 1, 1)] * 7)
 
 
+def tall_image(bands, rows_of_a_step, extra):
+    """21-byte rows (3 bands: they start on every byte of a dword), `extra` more of them than a launch's waves take in
+    one step: noise below 200 in the first step's rows, values from 200 up -- which occur nowhere else -- in the others."""
+    height = rows_of_a_step + extra
+    src = noise(21 // bands, height, bands, 23 + bands) % 200
+    src[rows_of_a_step:] = 200 + src[rows_of_a_step:] % 56
+    return np.ascontiguousarray(src)
+
+
+@pytest.mark.parametrize("bands", [3, 1])
+def test_hist_find_second_turn(bands):
+    """More rows than the launch has waves (a wave takes a row at a time): the counts of the values that only rows of
+    the second turn hold."""
+    rows_of_a_step = lib.vips_hip_hist_step(2) * lib.vips_hip_hist_step(1)
+    src = tall_image(bands, rows_of_a_step, 7)
+    assert src.shape[0] > rows_of_a_step and src[:rows_of_a_step].max() < 200 <= src[rows_of_a_step:].min()
+    want = Ref.run("hist_find", src)
+    with gated() as g:
+        got = Image.new_from_array(src).hist_find().numpy()
+    assert got.dtype == np.uint32 and got.shape == want.shape and np.array_equal(got, want)
+    assert int(got[0, 200:].sum()) == 7 * src.shape[1] * bands
+    assert sorted(g.report) == [HIST_GATE] and g.report[HIST_GATE][0] == 1, g.report
+
+
+def test_rectangles_second_turn():
+    """Six rectangles share a launch's blocks: each turns above a sixth of the rows (rounded down to blocks).  Windows
+    with left offsets 1 and 2 that end in rows only the second turn reaches."""
+    n = 6
+    rows_of_a_step = lib.vips_hip_hist_step(2) // n * lib.vips_hip_hist_step(1)
+    src = tall_image(3, rows_of_a_step, 9)
+    height = src.shape[0]
+    rects = [(0, 0, 7, height), (1, 0, 6, height), (2, 2, 5, height - 2), (0, 0, 7, rows_of_a_step), (3, 1, 1, height - 1), (0, 5, 2, height - 6)]
+    assert len(rects) == n and sum(h > rows_of_a_step for _, _, _, h in rects) == 5
+    im = Image.new_from_array(src)
+    with gated() as g:
+        got = im.hist_rects(rects)
+    assert g.report[HIST_GATE][0] == 1 and sorted(g.report) == [HIST_GATE]
+    for k, (left, top, w, h) in enumerate(rects):
+        window = np.ascontiguousarray(src[top:top + h, left:left + w])
+        want = Ref.run("hist_find", window)[0]
+        assert np.array_equal(got[k], want), (left, top, w, h)
+
+
 # ---- vips_smartcrop
 
 SCENE = ("scene200", lambda: scene(200, 150, 3, 5, 150, 100, 25))
